@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — TCCT `stc_tt` training hot path on MI355X: OCT B-scans/s, forward + losses + backward + clip + AdamW.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1: one rank per GPU.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`:
 WORLD_SIZE/RANK/LOCAL_RANK are then in the environment) or, when `--gpus N` arrives WITHOUT that environment, this process becomes a
@@ -11,8 +11,12 @@ exec), relays the child's one JSON line and exit code.  A line whose `n_gpus` di
 A "step" = one pass of the hot path over one synthetic minibatch of `--bs` B-scans (1x800x1100 each, already resident in
 HBM; loader-side prep = 1->3 channel replicate inside the NHWC conversion kernel + W zero-pad 1100->1104).  Workload at
 N=1 = BASELINE.json configs[1]: `stc_tt --los=di bs=8 1x800x1100 bf16`; other configs via --los=di+reg / di+reg+fpl.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed) and
-`cpu_baseline` (the oracle = CPU port of the reference path, timed on this box's host cores on a bounded sample).
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  A plain run does only that: set-up,
+warm-up, the timed steps, the line.  `--full` adds the measurements that take runs of their own: `roofline` (dominant kernels,
+HIP-event timed, before the training loop), `config.clip_adamw_ms`, `config.other_workloads` (--los=di+reg / di+reg+fpl at N=1) and
+`cpu_baseline` (the oracle = CPU port of the reference path, timed on the host cores on a bounded sample); the --no-* flags trim them.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs) as DIR/<name>.npy.  The timed steps update at learning rate 0
+(freeze_weights), so every step sees the same weights and two runs with the same arguments compute the same outputs up to rounding.
 """
 import argparse
 import json
@@ -42,6 +46,10 @@ def parse():
     p.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'fp32'])
     p.add_argument('--att', type=str, default='pool', choices=['pool', 'factor'],
                    help="token mixer: 'pool' = the reference's stc_tt (headline); 'factor' = its commented-out factorised attention (not the headline)")
+    p.add_argument('--full', action='store_true',
+                   help='also the measurements beyond the headline: roofline + copy ceiling, clip+AdamW alone, the other loss sets at N=1, the CPU baseline')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed step computed (loss, gradient norm, flat parameters / gradients, AdamW moments, BatchNorm buffers) as DIR/<name>.npy')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--no-roofline', action='store_true')
     p.add_argument('--no-other-workloads', action='store_true', help="skip the --los=di+reg / di+reg+fpl lines (`config.other_workloads`) that follow the headline loop at N=1")
@@ -64,6 +72,15 @@ def build_trainer(a, world):
     net = nets.RegNet(net, con=args.type_udh, out_channels=ds.out_channels)
     k = KiteSeg(model=net, dataset=ds, root=args.root, args=args)
     return k, ds, args
+
+
+def freeze_weights(k):
+    """The timed steps run the whole update -- clip + AdamW, the same launches and bytes as in training -- at learning rate 0, so that every
+    step starts from the same weights and a run computes the same thing every time.  The weight-gradient kernels sum with float atomics: one
+    step from the same weights differs between runs by rounding (~3e-7 in the gradients), but with lr > 0 those last bits move the weights, bf16
+    re-rounding and Adam's normalisation of near-zero gradients amplify them, and after 5 steps two runs' gradients differ by ~1e-2."""
+    for g in k.optimG.param_groups:
+        g['lr'] = 0.0
 
 
 class _StubTrainer:
@@ -300,6 +317,32 @@ def optimizer_ms(k, iters=20):
     return round(e0.elapsed_time(e1) / iters, 4)
 
 
+def dump_outputs(path, k, loss):
+    """--dump-outputs: what the last timed step computed, as a caller of train_step holds it afterwards -- the loss it returned, the
+    total gradient norm before clipping, the flat fp32 gradients, the parameters AdamW rewrote (unchanged at lr 0, see freeze_weights) and its
+    first / second moments (optimizer order), and the floating-point buffers of the model (BatchNorm running statistics, state_dict order).
+    ~16 MB at the default workload."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss': loss.detach().float().reshape(-1)}
+    f = getattr(k.optimG, '_flat', None)
+    if f is not None:
+        arrays['grad_total_norm'] = f['norm'].detach().float().reshape(-1)
+        arrays['params'] = f['p']
+        arrays['grads'] = f['g']
+        arrays['adam_m'] = f['m']
+        arrays['adam_v'] = f['v']
+    if hasattr(k, 'model'):
+        bufs = [b.detach().float().reshape(-1) for b in k.model.buffers() if b.is_floating_point()]
+        if bufs:
+            arrays['buffers'] = torch.cat(bufs)
+    total = sum(v.numel() * 4 for v in arrays.values())
+    if total > 64 * 2**20:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the 64 MB bound')
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), v.detach().to('cpu', torch.float32).numpy())
+
+
 def _cpu_model():
     try:
         for ln in open('/proc/cpuinfo'):
@@ -460,9 +503,6 @@ def main():
             local = local % torch.cuda.device_count()
         torch.cuda.set_device(local)
         dev = torch.device('cuda', local)
-    torch.manual_seed(2023 + rank)          # per-rank noise stream (DropPath masks, Gumbel / jitter draws): seed = base + rank, SURVEY 8(e)
-    if not stub:
-        torch.cuda.manual_seed_all(2023 + rank)
     if not stub and a.set:
         from tcct_amd import ops as _ops
         for kv in a.set.split(','):
@@ -481,15 +521,20 @@ def main():
     # The dominant-kernel timing runs BEFORE the training loop, on a quiet allocator: measured after it (27 GB pool live, two side streams
     # warm) the same kernel read 0.263 ms against 0.216-0.245 ms cold (round-2 review) -- ONE place, the cold one, is what the line reports.
     roof = copyc = None
-    if rank == 0 and not a.no_roofline and not stub:
+    if a.full and rank == 0 and not a.no_roofline and not stub:
         roof = dominant_kernel_roofline(a)
         copyc = copy_ceiling(a)
         torch.cuda.empty_cache()
+    # seeded after the roofline loops (which draw from the GPU generator), so that --full and a plain run train on the same draws
+    torch.manual_seed(2023 + rank)          # per-rank noise stream (DropPath masks, Gumbel / jitter draws): seed = base + rank, SURVEY 8(e)
+    if not stub:
+        torch.cuda.manual_seed_all(2023 + rank)
     if stub:
         tdist.init('gloo')
         k, img, lab = _StubTrainer(world, rank), None, None
     else:
         k, ds, args = build_trainer(a, world)
+        freeze_weights(k)
         k.model.train()
         batch = ds.make_batch(a.bs, seed=2023 + rank)
         img, lab, _, _ = ds.parse(batch)
@@ -517,6 +562,8 @@ def main():
     dt = time.perf_counter() - t0
     dt = tdist.max_over_ranks(dt, dev)
     lossv = float(loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, k, loss)
     devices = tdist.gather_strings('cpu (stub)' if stub else f'cuda:{local} ({torch.cuda.get_device_name(local)})')
     ranks_seen = None
     import torch.distributed as tdd0
@@ -543,6 +590,7 @@ def main():
                    'global_batch': a.bs * world, 'parallelism': f'dp{world}', 'ranks': ranks,
                    'backend': (tdd.get_backend() if tdd.is_initialized() else None), 'rank_devices': devices,
                    'grad_allreduce': getattr(k.optimG, 'allreduce_mode', 'none'), 'loss_last': round(lossv, 4),
+                   'update': None if stub else 'clip + AdamW at lr 0: every timed step starts from the same weights (freeze_weights)',
                    'step_ms_gpu_min_med_max': _min_med_max([marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]) if marks else None,
                    'step_ms_host_enqueue_min_med_max': _min_med_max([1e3 * (host[i + 1] - host[i]) for i in range(a.steps)]),
                    'slowest_step': max(range(a.steps), key=lambda i: host[i + 1] - host[i]),
@@ -555,8 +603,9 @@ def main():
             out['config']['nccl_version'] = '.'.join(str(v) for v in torch.cuda.nccl.version()) if tdd2.get_backend() == 'nccl' else None
         except Exception as e:                                  # noqa: BLE001
             out['config']['nccl_version'] = f'unavailable: {e}'
-    out['config']['clip_adamw_ms'] = None if stub else optimizer_ms(k)
-    if world == 1 and not stub and not a.no_other_workloads and not a.no_cpu_baseline and a.los == 'di':      # (the profiling / A-B tools all pass --no-cpu-baseline)
+    if a.full:
+        out['config']['clip_adamw_ms'] = None if stub else optimizer_ms(k)
+    if a.full and world == 1 and not stub and not a.no_other_workloads and not a.no_cpu_baseline and a.los == 'di':      # (the profiling / A-B tools all pass --no-cpu-baseline)
         # BASELINE.json configs[2] / [3] on the same box, in the same line (the headline `value` stays configs[1]): a fresh trainer per loss set -- the optimizer's
         # flat layout and the model's head composition depend on the loss flags -- 3 warm-up + 10 timed steps each, the same barrier-free single-rank timing.
         del k
@@ -565,6 +614,7 @@ def main():
         for los in ('di+reg', 'di+reg+fpl'):
             a2 = argparse.Namespace(**dict(vars(a), los=los))
             k2, ds2, _ = build_trainer(a2, world)
+            freeze_weights(k2)
             k2.model.train()
             b2 = ds2.make_batch(a.bs, seed=2023 + rank)
             i2, l2, _, _ = ds2.parse(b2)
@@ -589,7 +639,7 @@ def main():
         # whole-step view against the layer-granular traffic model of SURVEY §8(d): 7.38 GB (bf16) / 14.8 GB (fp32) per B-scan
         per_img = 7.38e9 if a.dtype == 'bf16' else 14.8e9
         out['roofline']['step_model_GBs'] = round(per_img * value / world / 1e9, 1)
-    if world == 1 and not a.no_cpu_baseline and not stub:
+    if a.full and world == 1 and not a.no_cpu_baseline and not stub:
         out['cpu_baseline'] = cpu_baseline(a)
     print(json.dumps(out), file=out_stream, flush=True)
     tdist.barrier()

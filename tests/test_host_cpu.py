@@ -284,8 +284,10 @@ def test_gradient_buckets_follow_the_backward_order():
 def test_bench_launcher_starts_the_ranks_as_children_and_fails_loudly():
     """`python bench.py --gpus 2` WITHOUT a torchrun environment must start two ranks itself (child process, torch.distributed.run) and
     relay their exit status: here (no GPU) the ranks refuse to run, and the launcher must report that instead of printing a 1-rank
-    line.  With WORLD_SIZE set the process is a rank: a mismatch with --gpus is an error."""
+    line.  With WORLD_SIZE set the process is a rank: a mismatch with --gpus is an error.  The GPUs are hidden from the children, so that
+    the ranks find none on a host that has one too (there two ranks on one GPU would fail for another reason)."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    env.update(HIP_VISIBLE_DEVICES='-1', CUDA_VISIBLE_DEVICES='-1')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0'],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode != 0
