@@ -47,6 +47,16 @@ static inline int tcct_grid(int64_t work_items, int block, int cap = 256 * 16) {
     return (int)g;
 }
 
+// THE launch of a kernel that may need more than the default 64 KB of dynamic LDS: raises the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to MAX_LDS_BYTES, then
+// launches.  The attribute is set once per kernel instantiation and process (a function-local static: initialised exactly once whichever thread comes first; one
+// process drives one GPU in this project) and its status is ignored: a launch that asks for more LDS than was granted fails and the caller's TCCT_LAUNCH_OK reports it.
+template <auto Kern, int MAX_LDS_BYTES, typename... Args>
+static void tcct_launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    static const hipError_t once = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_BYTES);
+    (void)once;
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+}
+
 // ---------------------------------------------------------------- scalar / vec4 loads (compute is fp32)
 __device__ __forceinline__ float ldf(const float* p) { return *p; }
 __device__ __forceinline__ float ldf(const bf16* p) { return __bfloat162float(*p); }
@@ -198,6 +208,30 @@ __device__ __forceinline__ void affine4(float* v, const float* a, const float* b
 __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // no instruction: wave-scope ordering only constrains the optimizer
 }
+
+// ---------------------------------------------------------------- global -> LDS DMA (the row-streaming convolution kernels)
+typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4;
+__device__ __forceinline__ void lds_dma16(const u32x4& rsrc, uint32_t voff, uint32_t lds_addr) {
+    // 64 lanes x 16 B from per-lane buffer offsets to LDS bytes [lds_addr + 16 lane ..): inline asm on purpose -- the builtin form makes hipcc treat the DMA as a
+    // pending LDS store and drain it (vmcnt(0)) in front of the next ds_read.  M0 (the LDS base) is compiler-reserved: saved and restored.
+    unsigned keep;
+    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_addr) : "memory");
+}
+__device__ __forceinline__ u32x4 make_rsrc_words(const void* base, uint32_t bytes) {
+    const uint64_t b = (uint64_t)base;
+    u32x4 d;
+    d[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
+    d[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);
+    d[2] = __builtin_amdgcn_readfirstlane(bytes);
+    d[3] = 0x00020000u;
+    return d;
+}
+
+// v as it reads back after being stored as T (bf16: rounded to nearest even; fp32: unchanged)
+template <typename T> __device__ __forceinline__ float round_as(float v);
+template <> __device__ __forceinline__ float round_as<float>(float v) { return v; }
+template <> __device__ __forceinline__ float round_as<bf16>(float v) { return __bfloat162float(__float2bfloat16(v)); }
 
 // Workgroup b of a launch runs on XCD b % 8 (round-robin dispatch) and every XCD has its own L2: blocks that share input rows (resize, stencils)
 // should be neighbours on ONE XCD.  xcd_band maps the hardware's linear block id to a logical one such that XCD x owns the contiguous band

@@ -20,7 +20,6 @@
 
 typedef __attribute__((ext_vector_type(8))) __bf16 ch_bf16x8;
 typedef __attribute__((ext_vector_type(16))) float ch_f32x16;
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int ch_u32x4;
 
 #define CH_T 256
 #define CH_R 9                  // producer ring rows (a multiple of 3: ring slot and accumulator index are compile-time in the 9-fold unrolled body)
@@ -30,22 +29,6 @@ typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int 
 #define CH_SW 30                // output pixels per strip
 #define CH_OOB 0x80000000u
 
-__device__ __forceinline__ void ch_lds_dma16(const ch_u32x4& rsrc, uint32_t voff, uint32_t lds_addr) {
-    // 64 lanes x 16 B from per-lane buffer offsets to LDS bytes [lds_addr + 16 lane ..) (see lds_dma16 in conv_mfma.hip: inline asm so that hipcc does not drain
-    // the DMA in front of the next ds_read; M0 saved and restored)
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ ch_u32x4 ch_rsrc_words(const void* base, uint32_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    ch_u32x4 d;
-    d[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    d[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);
-    d[2] = __builtin_amdgcn_readfirstlane(bytes);
-    d[3] = 0x00020000u;
-    return d;
-}
 // LDS writes of this wave have landed, then the block barrier: the hand-over of a mid row.  (__syncthreads() would also drain vmcnt -- the DMA pipeline.)
 __device__ __forceinline__ void ch_row_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -107,7 +90,7 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
     if (producer) {
         // ---------------------------------------------------------------------------------------------- convolution 1
         // iteration t: input halo row t (image row r0 - 2 + t) arrives; mid row m = t - 2 (image row r0 - 1 + m, m = 0 .. L + 1) is complete after its MFMAs
-        const ch_u32x4 rx = ch_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
+        const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
         const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(mid + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
         const int pq = lane >> 2, cs = (lane & 3) ^ ((lane >> 4) & 3);          // LDS position lane & 3 of ring pixel 16 piece + pq holds chunk cs
         const int c0 = w0 - 2 + pq, c1 = w0 + 14 + pq, c2 = w0 + 30 + pq;
@@ -133,9 +116,9 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
             const bool xin = a <= L + 3 && ri >= 0 && ri < H;
             const uint32_t ro = (uint32_t)(xin ? ri : 0) * rowb;
             const uint32_t base = ring_lds + (uint32_t)(slot * CH_ROWB);
-            ch_lds_dma16(rx, xin ? o0 + ro : CH_OOB, base);
-            ch_lds_dma16(rx, xin ? o1 + ro : CH_OOB, base + 1024u);
-            if (lane < 8) ch_lds_dma16(rx, xin ? o2 + ro : CH_OOB, base + 2048u);
+            lds_dma16(rx, xin ? o0 + ro : CH_OOB, base);
+            lds_dma16(rx, xin ? o1 + ro : CH_OOB, base + 1024u);
+            if (lane < 8) lds_dma16(rx, xin ? o2 + ro : CH_OOB, base + 2048u);
         };
 #pragma unroll
         for (int a = 0; a < CH_P; ++a) issue(a, a);
@@ -188,9 +171,9 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
                 }
                 ch_row_barrier();                       // B_t: mid row t - 2 is in LDS for the consumer
                 // ... and goes to HBM from the same slot (rows r0 .. r0 + L - 1 only: the two halo mid rows belong to the neighbouring runs)
-                ch_u32x4 pend[2];
+                u32x4 pend[2];
 #pragma unroll
-                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const ch_u32x4*>(slot + sl[u]);
+                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(slot + sl[u]);
                 const bool own = m >= 1 && m <= L && mid != nullptr;      // mid == NULL (inference): the intermediate lives in LDS only
                 const uint32_t oro = (uint32_t)(own ? mrow : 0) * rowb;
 #pragma unroll
@@ -271,9 +254,9 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
 #pragma unroll
                 for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(scr + r * 64 + ((q ^ f) << 4) + hh * 8) = ov[q];
                 wave_lds_fence();
-                ch_u32x4 pend[2];
+                u32x4 pend[2];
 #pragma unroll
-                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const ch_u32x4*>(scr + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
+                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(scr + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
                 wave_lds_fence();
                 const uint32_t oro = (uint32_t)(ovalid ? r0 + o : 0) * rowb;
 #pragma unroll
@@ -342,13 +325,9 @@ extern "C" int tcct_conv32_chain33(const void* x, const void* wp1, const float* 
     TCCT_CHECK(blocks < (1LL << 31), "conv32_chain33: too many blocks");
     const size_t lds = (size_t)2 * CH_R * CH_ROWB + (size_t)2 * CH_MR * CH_ROWB + 2 * 2048 + 64 * 4 + 128 * 4;
     hipStream_t st = (hipStream_t)stream;
-#define CH_LAUNCH(M)                                                                                                                                          \
-    do {                                                                                                                                                      \
-        static bool attr = false;                                                                                                                             \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_chain33<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; }       \
-        hipLaunchKernelGGL((k_conv32_chain33<M>), dim3((unsigned)blocks), dim3(CH_T), lds, st, (const bf16*)x, (const bf16*)wp1, bias1, (bf16*)mid,            \
-                           (const bf16*)wp2, bias2, (bf16*)y, (const bf16*)res, N, H, W, strips, run, rpi, stats);                                             \
-    } while (0)
+#define CH_LAUNCH(M)                                                                                                                                  \
+    tcct_launch<k_conv32_chain33<M>, 80 * 1024>(dim3((unsigned)blocks), dim3(CH_T), lds, st, (const bf16*)x, (const bf16*)wp1, bias1, (bf16*)mid,     \
+                                                (const bf16*)wp2, bias2, (bf16*)y, (const bf16*)res, N, H, W, strips, run, rpi, stats)
     if (stats) CH_LAUNCH(2);
     else if (res) CH_LAUNCH(3);
     else CH_LAUNCH(0);

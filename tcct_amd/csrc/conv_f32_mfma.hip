@@ -183,14 +183,8 @@ static int conv32f_fwd_impl(const float* x, const float* wp, const float* bias, 
     TCCT_CHECK(nt > 0 && nt < (1LL << 31), "conv32f_fwd: bad tile count");
     const int grid = (int)(nt < 256 ? nt : 256);
     hipStream_t st = (hipStream_t)stream;
-    static bool attr[2] = {false, false};
-    if (vert) {
-        if (!attr[1]) { (void)hipFuncSetAttribute((const void*)k_conv32f_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr[1] = true; }
-        hipLaunchKernelGGL(k_conv32f_mfma<true>, dim3(grid), dim3(CFB), lds, st, x, wp, bias, y, yadd, N, H, W, KH, KW, PH, PW, tilesH, tilesW, (int)nt, xs, xo, ys, yo);
-    } else {
-        if (!attr[0]) { (void)hipFuncSetAttribute((const void*)k_conv32f_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr[0] = true; }
-        hipLaunchKernelGGL(k_conv32f_mfma<false>, dim3(grid), dim3(CFB), lds, st, x, wp, bias, y, yadd, N, H, W, KH, KW, PH, PW, tilesH, tilesW, (int)nt, xs, xo, ys, yo);
-    }
+    if (vert) tcct_launch<k_conv32f_mfma<true>, 160 * 1024>(dim3(grid), dim3(CFB), lds, st, x, wp, bias, y, yadd, N, H, W, KH, KW, PH, PW, tilesH, tilesW, (int)nt, xs, xo, ys, yo);
+    else tcct_launch<k_conv32f_mfma<false>, 160 * 1024>(dim3(grid), dim3(CFB), lds, st, x, wp, bias, y, yadd, N, H, W, KH, KW, PH, PW, tilesH, tilesW, (int)nt, xs, xo, ys, yo);
     TCCT_LAUNCH_OK();
 }
 
@@ -358,8 +352,7 @@ static int conv32f_wgrad_impl(const float* x, const float* dy, float* dw, float*
     TCCT_CHECK(nt > 0 && nt < (1LL << 31), "conv32f_wgrad: bad tile count");
     int64_t g8 = (nt + 7) / 8;                  // >= 8 tiles per block: every block ends with KH*KW*1024 same-address atomics
     const int grid = (int)(g8 < 1 ? 1 : (g8 > 256 ? 256 : g8));
-#define WG_L(V, NT) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_conv32f_wgrad<V, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_conv32f_wgrad<V, NT>), dim3(grid), dim3(CFB), lds, st, x, dy, dw, dbias, N, H, W, KH, KW, PH, PW, tilesH, tilesW, (int)nt, xs, xo, ds, dof, ldi, o_off, i_off); }
+#define WG_L(V, NT) tcct_launch<k_conv32f_wgrad<V, NT>, 160 * 1024>(dim3(grid), dim3(CFB), lds, st, x, dy, dw, dbias, N, H, W, KH, KW, PH, PW, tilesH, tilesW, (int)nt, xs, xo, ds, dof, ldi, o_off, i_off);
     const int taps = KH * KW;
     if (vert) { if (taps <= 9) WG_L(true, 9) else WG_L(true, 13) }
     else { if (taps <= 9) WG_L(false, 9) else WG_L(false, 13) }
@@ -538,8 +531,6 @@ extern "C" int tcct_pwf_wgrad(const float* x, const float* dy, float* dw, float*
     }
     const size_t lds = (size_t)128 * (N + 32 * PF_KTB) * 4;
     TCCT_CHECK(lds <= 160 * 1024, "pwf_wgrad: %zu B of LDS", lds);
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_pwf_wgrad, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     const int64_t tiles = (M + 127) / 128;
     const int gy = (K / 32 + PF_KTB - 1) / PF_KTB;
     // no register prefetch in this kernel: several resident blocks per CU hide the load latency instead (48 KB of LDS at N = 32: three per CU;
@@ -551,6 +542,6 @@ extern "C" int tcct_pwf_wgrad(const float* x, const float* dy, float* dw, float*
     if (gx < 32) gx = 32;
     if (gx > (tiles + 7) / 8) gx = (tiles + 7) / 8;        // >= 8 tiles per block: every block ends with same-address atomics on all of dw
     if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(k_pwf_wgrad, dim3((unsigned)gx, gy), dim3(CFB), lds, st, x, dy, dw, dbias, M, K, N, tiles);
+    tcct_launch<k_pwf_wgrad, 160 * 1024>(dim3((unsigned)gx, gy), dim3(CFB), lds, st, x, dy, dw, dbias, M, K, N, tiles);
     TCCT_LAUNCH_OK();
 }

@@ -13,7 +13,6 @@
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4;
 
 #define MB 256
 #define OOB_OFF 0x80000000u     // buffer offset beyond every descriptor range used here (< 2 GiB): loads return 0, stores are dropped
@@ -539,9 +538,7 @@ static int conv32_fwd_impl(const void* x, const void* wp, const float* bias, voi
     }
 #define CF_LAUNCH(V, S, KHT, KWT)                                                                                           \
     do {                                                                                                                    \
-        static bool attr = false;                                                                                           \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_mfma<V, S, KHT, KWT>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_conv32_mfma<V, S, KHT, KWT>), dim3(grid), dim3(MB), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, \
+        tcct_launch<k_conv32_mfma<V, S, KHT, KWT>, 80 * 1024>(dim3(grid), dim3(MB), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, \
                            KH, KW, PH, PW, tilesH, tilesW, (int)nt, xs, xo, ys, yo, accum, stats, stat_pre, aff, aff_post, (const bf16*)yadd, stats_sq_off);                \
     } while (0)
 #define CF_S(V, KHT, KWT)                                                                                   \
@@ -962,22 +959,7 @@ k_conv32_wgrad33_roll(const bf16* __restrict__ x, const bf16* __restrict__ dy, f
 #define WS_P 7                  // rows in flight
 #define WS_ROWB 2176            // 18 x pixels (1152 B) + 16 dy pixels (1024 B)
 #define WS_MIN_RUN 32            // rows per wave below which the pipeline fill (7 rows per segment) costs more than the tiles' barriers: levels 0-1 stream, 2-4 roll
-__device__ __forceinline__ void lds_dma16(const u32x4& rsrc, uint32_t voff, uint32_t lds_addr) {
-    // 64 lanes x 16 B from per-lane buffer offsets to LDS bytes [lds_addr + 16 lane ..): inline asm on purpose -- the builtin form makes hipcc treat the DMA as a
-    // pending LDS store and drain it (vmcnt(0)) in front of the next ds_read.  M0 (the LDS base) is compiler-reserved: saved and restored.
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ u32x4 make_rsrc_words(const void* base, uint32_t bytes) {
-    const uint64_t b = (uint64_t)base;
-    u32x4 d;
-    d[0] = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    d[1] = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);
-    d[2] = __builtin_amdgcn_readfirstlane(bytes);
-    d[3] = 0x00020000u;
-    return d;
-}
+// (lds_dma16 / make_rsrc_words: common.h)
 __global__ void __launch_bounds__(WS_T, 2)
 k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, float* __restrict__ dw, float* __restrict__ dbias,
                         int N, int H, int W, int strips, int run) {
@@ -1318,9 +1300,7 @@ static bool conv32_fwd33_stream_launch(const void* x, const void* wp, const floa
     const size_t lds = (size_t)nw * FS_R * FS_ROWB + 128 + (size_t)nw * 256;
 #define FS_LAUNCH(S)                                                                                                                                          \
     do {                                                                                                                                                      \
-        static bool attr = false;                                                                                                                             \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_fwd33_stream<S>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_conv32_fwd33_stream<S>), dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, \
+        tcct_launch<k_conv32_fwd33_stream<S>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, \
                            run, rpi, stats, stats_sq_off, aff);                                                                                                  \
     } while (0)
     if (stat_code == 0) FS_LAUNCH(0);
@@ -1474,9 +1454,7 @@ static bool conv32_fwd1k_stream_launch(const void* x, const void* wp, const floa
     if (!force && (H < FS_MIN_RUN || blocks < 384)) return false;
 #define F1_LAUNCH(KK)                                                                                                                                          \
     do {                                                                                                                                                      \
-        static bool attr = false;                                                                                                                             \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_fwd1k_stream<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_conv32_fwd1k_stream<KK>), dim3((unsigned)blocks), dim3(64 * nw), (size_t)nw * F1_R * (32 + KK - 1) * 64 + 128, st, (const bf16*)x, (const bf16*)wp, \
+        tcct_launch<k_conv32_fwd1k_stream<KK>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), (size_t)nw * F1_R * (32 + KK - 1) * 64 + 128, st, (const bf16*)x, (const bf16*)wp, \
                            bias, (bf16*)y, N, H, W, strips, run, rpi);                                                                                      \
     } while (0)
     if (K == 13) F1_LAUNCH(13);
@@ -1636,9 +1614,7 @@ static bool conv32_fwdk1_stream_launch(const void* x, const void* wp, const floa
     if (!force && (H < 2 * FS_MIN_RUN || blocks < 384)) return false;
 #define FV_LAUNCH(KK)                                                                                                                                          \
     do {                                                                                                                                                      \
-        static bool attr = false;                                                                                                                             \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_fwdk1_stream<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_conv32_fwdk1_stream<KK>), dim3((unsigned)blocks), dim3(64 * nw), (size_t)KK * 2048 + (size_t)nw * FV_R * 2048 + 128, st, (const bf16*)x, \
+        tcct_launch<k_conv32_fwdk1_stream<KK>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), (size_t)KK * 2048 + (size_t)nw * FV_R * 2048 + 128, st, (const bf16*)x, \
                            (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, run, rpi);                                                                     \
     } while (0)
     if (K == 13) FV_LAUNCH(13);
@@ -2059,21 +2035,16 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
             if (run < 12) run = 12;                 // small maps: fewer, longer runs (the pipeline fill is 7 rows)
             blocks = (int)((rows + run - 1) / run);
             constexpr size_t ldss = (size_t)(WS_T / 64) * WS_R * WS_ROWB;
-            static bool attrs = false;
-            if (!attrs) { (void)hipFuncSetAttribute((const void*)k_conv32_wgrad33_stream, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attrs = true; }
-            hipLaunchKernelGGL(k_conv32_wgrad33_stream, dim3((unsigned)blocks), dim3(WS_T), ldss, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run);
+            tcct_launch<k_conv32_wgrad33_stream, 80 * 1024>(dim3((unsigned)blocks), dim3(WS_T), ldss, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run);
             tcct_census_hit(TCCT_CENSUS_WGRAD33_STREAM);
             TCCT_LAUNCH_OK();
         }
     }
     if ((m33 == 0 || m33 == 2) && sq && ldi == 32 && o_off == 0 && i_off == 0 && xo == 0 && dof == 0) {      // plain 3x3: rolling rows, 6 waves x 2 blocks per CU
         constexpr size_t lds4 = (size_t)18 * 34 * 64 + 16 * 32 * 64;
-        static bool attr4 = false;
-        if (!attr4) { (void)hipFuncSetAttribute((const void*)k_conv32_wgrad33_roll, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr4 = true; }
         // (`grid`: <= 128 blocks on the small maps this kernel serves -- 96-936 tiles at levels 2-4 --: one block per tile spent more time in the 9 216 closing atomics than in
         // its tile, 4.7 M atomics at level 2)
-        hipLaunchKernelGGL(k_conv32_wgrad33_roll, dim3((unsigned)grid), dim3(WR_T), lds4, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W,
-                           tilesH, tilesW, (int)nt);
+        tcct_launch<k_conv32_wgrad33_roll, 80 * 1024>(dim3((unsigned)grid), dim3(WR_T), lds4, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, tilesH, tilesW, (int)nt);
         TCCT_LAUNCH_OK();
     }
     // 1 x K / K x 1 with K = 13, 11 on maps whose waves get long runs (levels 0-1): all taps in one wave per SIMD (mode 3 forces it, mode 4 keeps the shifted lines)
@@ -2090,9 +2061,7 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
     do {                                                                                                                    \
         constexpr size_t ring = (size_t)(WK_T / 64) * WK_R * ((V ? 16 : 16 + KK - 1) + 16) * 64, redb = (size_t)KK * 4096;                                     \
         constexpr size_t ldsk = ring > redb ? ring : redb;                                                                                                     \
-        static bool attr = false;                                                                                           \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_wgradk_stream<KK, V>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_conv32_wgradk_stream<KK, V>), dim3((unsigned)blocks), dim3(WK_T), ldsk, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run); \
+        tcct_launch<k_conv32_wgradk_stream<KK, V>, 160 * 1024>(dim3((unsigned)blocks), dim3(WK_T), ldsk, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run); \
     } while (0)
             if (TAPS == 13) { if (vert) WK_LAUNCH(13, true); else WK_LAUNCH(13, false); }
             else { if (vert) WK_LAUNCH(11, true); else WK_LAUNCH(11, false); }
@@ -2106,9 +2075,7 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
         xo == 0 && dof == 0) {      // 1 x K / K x 1 at levels 0-2: shifted lines
 #define WL_LAUNCH(KK, V)                                                                                                     \
     do {                                                                                                                    \
-        static bool attr = false;                                                                                           \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_wgrad_line<KK, V>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_conv32_wgrad_line<KK, V>), dim3(grid), dim3(MB), (size_t)(8 * (64 + KK - 1) + 16) * 64 + 512 * 64, st, (const bf16*)x, (const bf16*)dy, \
+        tcct_launch<k_conv32_wgrad_line<KK, V>, 80 * 1024>(dim3(grid), dim3(MB), (size_t)(8 * (64 + KK - 1) + 16) * 64 + 512 * 64, st, (const bf16*)x, (const bf16*)dy, \
                            dw, dbias, N, H, W, tilesH, tilesW, (int)nt);                                                    \
     } while (0)
         if (TAPS == 13) { if (vert) WL_LAUNCH(13, true); else WL_LAUNCH(13, false); }
@@ -2124,9 +2091,7 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
     TCCT_CHECK(LH * LW * 4 <= MAXL * MB, "conv32_wgrad: %dx%d tile image exceeds the staging slots", KH, KW);
 #define WG_LAUNCH(TPW, V, Q)                                                                                                 \
     do {                                                                                                                    \
-        static bool attr = false;                                                                                           \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_wgrad<TPW, V, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_conv32_wgrad<TPW, V, Q>), dim3(grid), dim3(MB), lds, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, KH, \
+        tcct_launch<k_conv32_wgrad<TPW, V, Q>, 80 * 1024>(dim3(grid), dim3(MB), lds, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, KH, \
                            KW, PH, PW, TG, tilesH, tilesW, (int)nt, xs, xo, ds, dof, ldi, o_off, i_off);                                                        \
     } while (0)
     if (sq) WG_LAUNCH(5, false, true);
@@ -2396,9 +2361,7 @@ extern "C" int tcct_conv32_bwd3x3(const void* x, const void* dy, const void* wp_
     TCCT_CHECK(nt > 0 && nt < (1LL << 31), "conv32_bwd3x3: bad tile count");
     const size_t lds = 9 * 2048 + (size_t)18 * 34 * 64 + (size_t)18 * 34 * IPS + 4096;
     const int grid = (int)(nt < 256 ? nt : 256);
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_conv32_bwd33<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    hipLaunchKernelGGL((k_conv32_bwd33<0>), dim3(grid), dim3(BWD_T), lds, st, (const bf16*)x, (const bf16*)dy, (const bf16*)wp_t, (const bf16*)dskip,
+    tcct_launch<k_conv32_bwd33<0>, 160 * 1024>(dim3(grid), dim3(BWD_T), lds, st, (const bf16*)x, (const bf16*)dy, (const bf16*)wp_t, (const bf16*)dskip,
                        (bf16*)dx, dw, dbias, N, H, W, tilesH, tilesW, (int)nt);
     TCCT_LAUNCH_OK();
 }

@@ -116,8 +116,6 @@ template <int STRIDE> struct DwChunk {
 // stats != NULL (VEC == 4 only): also accumulate per-channel sum / sum of squares of y AS STORED into stats[0..C) / stats[C..2C) (fp64, zero on
 // entry) -- the statistics of the train-mode BatchNorm behind the convolution (InvRes: dwconv -> norm, reference nets/tcct.py:548-551), which
 // otherwise cost a separate pass over y
-__device__ __forceinline__ float dw_rnd(float v, const bf16*) { return __bfloat162float(__float2bfloat16(v)); }
-__device__ __forceinline__ float dw_rnd(float v, const float*) { return v; }
 // Round 4: the convolution's input may be y_prev, the input of a train-mode BatchNorm + Hardswish whose normalisation pass was never run (xab = {a[C], b[C]}):
 // z = hswish(a y_prev + b) is applied to every channel vector ONCE, when its row enters the register window, and rounded to the activation type -- the
 // value the separate normalisation pass stored.  Elements outside the image stay zero (the convolution pads z, not y_prev).
@@ -255,12 +253,12 @@ __global__ void __launch_bounds__(DB) k_dw_fwd(const T* __restrict__ x, const fl
 #pragma unroll
                             for (int k = 0; k < VEC; ++k) {
                                 const float yv = RS[j][cc].get(k), u = xa[k] * yv + xb[k];
-                                const float d = dw_rnd(acc[k], (const T*)nullptr) * (u < -3.f ? 0.f : (u <= 3.f ? (2.f * u + 3.f) * (1.f / 6.f) : 1.f));
+                                const float d = round_as<T>(acc[k]) * (u < -3.f ? 0.f : (u <= 3.f ? (2.f * u + 3.f) * (1.f / 6.f) : 1.f));
                                 st_s[k] += (SAcc)d; st_q[k] += (SAcc)d * (SAcc)yv;
                             }
                         } else {
 #pragma unroll
-                            for (int k = 0; k < VEC; ++k) { const SAcc r = dw_rnd(acc[k], (const T*)nullptr); st_s[k] += r; st_q[k] += r * r; }
+                            for (int k = 0; k < VEC; ++k) { const SAcc r = round_as<T>(acc[k]); st_s[k] += r; st_q[k] += r * r; }
                         }
                     }
                 }

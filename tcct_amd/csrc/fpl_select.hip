@@ -441,28 +441,22 @@ extern "C" int tcct_fpl_select(const void* feat, const uint8_t* labels, const fl
     if (hipMemsetAsync(tickets, 0, sizeof(uint32_t) * 8, st) != hipSuccess) { tcct_set_error("fpl_select: memset failed"); return -2; }
     if (hipMemsetAsync(pro_sum, 0, sizeof(float) * C * FS_BINS * 32, st) != hipSuccess) { tcct_set_error("fpl_select: memset failed"); return -2; }
     const size_t lds_h = (size_t)FS_SLOTS * 128 * 4 + (size_t)FS_MAXC * FS_BINS * 8 + (FS_MAXC + 1) * 4;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_fs_hist, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); attr = true; }      // + ~2 KB static (the resolve step)
     int grid = tcct_grid(M, FS_TB, 256);            // one 1024-thread block per CU (128 blocks: 0.46 ms for the seven levels against 0.33)
     if ((M + grid - 1) / grid > FS_BLOCK_PIX) grid = (int)((M + FS_BLOCK_PIX - 1) / FS_BLOCK_PIX);       // 16-bit block-private counters
     TCCT_CHECK(nlevels <= 8, "fpl_select: %d radix levels", nlevels);
     const int passes = (C * FS_BINS + FS_SLOTS - 1) / FS_SLOTS;
     for (int level = 0; level < nlevels; ++level)           // histogram of the level + (in its last block) the resolve step: one launch
-        hipLaunchKernelGGL(k_fs_hist, dim3(grid, level == 0 ? 1 : passes), dim3(FS_TB), lds_h, st, labels, prob, M, C, level, ib, tb, passes, nlevels, state, hist, tickets);
+        tcct_launch<k_fs_hist, 128 * 1024>(dim3(grid, level == 0 ? 1 : passes), dim3(FS_TB), lds_h, st, labels, prob, M, C, level, ib, tb, passes, nlevels, state, hist, tickets);     // 128 KB + ~2 KB static (the resolve step)
     hipLaunchKernelGGL(k_fs_assign, dim3(tcct_grid(M, FS_TB, 1024)), dim3(FS_TB), 0, st, labels, prob, M, C, ib, (const FplState*)state, binmap);
     const size_t lds_a = (size_t)C * FS_BINS * 32 * 4;
     const int gb = tcct_grid((M / FS_RUN + 1) * 8, FS_TB, 512);
     if (dtype == TCCT_F32) {
-        static bool a32 = false;
-        if (!a32) { (void)hipFuncSetAttribute((const void*)k_fs_binsum<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a32 = true; }
-        hipLaunchKernelGGL(k_fs_binsum<float>, dim3(gb), dim3(FS_TB), lds_a, st, (const float*)feat, labels, (const uint8_t*)binmap, M, C, pro_sum);
-    } else if (dtype == TCCT_BF16) {
-        static bool a16 = false;
-        if (!a16) { (void)hipFuncSetAttribute((const void*)k_fs_binsum<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a16 = true; }
-        (void)a16;
+        tcct_launch<k_fs_binsum<float>, 160 * 1024>(dim3(gb), dim3(FS_TB), lds_a, st, (const float*)feat, labels, (const uint8_t*)binmap, M, C, pro_sum);
+    } else if (dtype == TCCT_BF16) {            // (k_fs_binsum<bf16>, the scalar form of the same sum, stays compiled for comparison: instantiated below)
         const int64_t tiles = (M + 127) / 128;
         hipLaunchKernelGGL(k_fs_binsum_mfma, dim3((unsigned)(tiles < 1536 ? tiles : 1536)), dim3(256), 0, st, (const bf16*)feat, labels, (const uint8_t*)binmap, M, C, pro_sum);
     } else { tcct_set_error("fpl_select: bad dtype %d", dtype); return -1; }
     if (hipMemcpyAsync(counts, state->counts, sizeof(uint32_t) * FS_MAXC, hipMemcpyDeviceToDevice, st) != hipSuccess) { tcct_set_error("fpl_select: copy failed"); return -2; }
     TCCT_LAUNCH_OK();
 }
+template __global__ void k_fs_binsum<bf16>(const bf16*, const uint8_t*, const uint8_t*, int64_t, int, float*);

@@ -12,9 +12,6 @@
 #include "common.h"
 
 #define LP_T 256
-template <typename T> __device__ __forceinline__ float round_to(float v);
-template <> __device__ __forceinline__ float round_to<float>(float v) { return v; }
-template <> __device__ __forceinline__ float round_to<bf16>(float v) { return __bfloat162float(__float2bfloat16(v)); }
 
 struct f8 { float v[8]; };
 __device__ __forceinline__ f8 ld8(const float* p) {
@@ -123,7 +120,7 @@ k_ln_metapool_fwd(const T* __restrict__ t, T* __restrict__ y, int N, int C, cons
         row_stats<LP>(x, act, invC, eps, mean, rstd);
         const bool in = nn >= 0 && nn < N;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) ctr.v[k] = (in && act) ? round_to<T>((x.v[k] - mean) * rstd * gam[k] + bet[k]) : 0.f;
+        for (int k = 0; k < 8; ++k) ctr.v[k] = (in && act) ? round_as<T>((x.v[k] - mean) * rstd * gam[k] + bet[k]) : 0.f;
         return widen<LP>(ctr, hasl, hasr);
     };
     const Raw8<T> r0 = fetch(n0 - 1), r1 = fetch(n0);
@@ -153,7 +150,7 @@ k_ln_metapool_fwd(const T* __restrict__ t, T* __restrict__ y, int N, int C, cons
                 if (LN2) {                                  // the second LayerNorm reads the STORED row: round first
                     f8 orr;
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) orr.v[k] = act ? round_to<T>(o.v[k]) : 0.f;
+                    for (int k = 0; k < 8; ++k) orr.v[k] = act ? round_as<T>(o.v[k]) : 0.f;
                     float mean2, rstd2;
                     row_stats<LP>(orr, act, invC, eps2, mean2, rstd2);
                     if (gl == 0) { mean_rstd2[2 * (img + n)] = mean2; mean_rstd2[2 * (img + n) + 1] = rstd2; }
@@ -230,7 +227,7 @@ k_ln_metapool_bwd(const T* __restrict__ t, const T* __restrict__ dy, T* __restri
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {
                         const float s_ = (prev.g[k] + cur.g[k] + nxt.g[k]) + (prev.g[k + 1] + cur.g[k + 1] + nxt.g[k + 1]) + (prev.g[k + 2] + cur.g[k + 2] + nxt.g[k + 2]);
-                        const float da = act ? round_to<T>(sc * (s_ - dcur.v[k])) : 0.f;
+                        const float da = act ? round_as<T>(sc * (s_ - dcur.v[k])) : 0.f;
                         const float h = act ? (xc.v[k] - mean) * rstd : 0.f;
                         xh[k] = h;
                         ag[k] += da * h;

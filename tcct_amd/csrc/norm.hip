@@ -446,8 +446,6 @@ extern "C" int tcct_bn_sums_from_raw(const double* raw, const float* mean_rstd, 
 // the activation kinds are template constants for the combination the network uses (PRE/POST = -1: run-time kinds; the first version,
 // with act_fwd's per-element switch and the window maxima recomputed in both backward kernels, ran at 2.3 - 2.9 TB/s and was SLOWER than
 // the three separate kernels: 0.94 vs 0.68 ms at level 0).
-__device__ __forceinline__ float rnd_as(float v, const bf16*) { return __bfloat162float(__float2bfloat16(v)); }
-__device__ __forceinline__ float rnd_as(float v, const float*) { return v; }
 
 template <typename T, int PRE, int POST>
 __global__ void k_bn_pool_fwd(const T* __restrict__ x, T* __restrict__ zout, T* __restrict__ pooled, unsigned char* __restrict__ amax, int N, int H,
@@ -475,7 +473,7 @@ __global__ void k_bn_pool_fwd(const T* __restrict__ x, T* __restrict__ zout, T* 
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float z = rnd_as(actf<POST>(post_act, a_[k] * actf<PRE>(pre_act, v[q].v[k]) + b_[k]), (const T*)nullptr);
+                const float z = round_as<T>(actf<POST>(post_act, a_[k] * actf<PRE>(pre_act, v[q].v[k]) + b_[k]));
                 v[q].v[k] = z;
                 if (q == 0) m.v[k] = z;
                 else if (z > m.v[k] || z != z) { m.v[k] = z; am = (am & ~(3u << (2 * k))) | ((unsigned)q << (2 * k)); }

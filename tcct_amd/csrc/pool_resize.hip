@@ -799,9 +799,6 @@ extern "C" int tcct_l2norm_bwd_scaled_add(const void* x, const void* dy, const v
 // (k_fpl_bwd is gone from the step) and the two resize gradients read 2 bytes per contributing pixel instead of 64.  Values are rounded to the
 // storage type first, exactly as the tensor used to hold them.
 #define FG_BINS 32
-template <typename T> __device__ __forceinline__ float fg_round(float v);
-template <> __device__ __forceinline__ float fg_round<float>(float v) { return v; }
-template <> __device__ __forceinline__ float fg_round<bf16>(float v) { return __bfloat162float(__float2bfloat16(v)); }
 
 // dx = oscale * l2norm_bwd(x, dfeat) + res  (C = 32: eight lanes per pixel)
 template <typename T>
@@ -826,7 +823,7 @@ __global__ void k_l2norm_bwd_fplgrad(const T* __restrict__ x, const uint8_t* __r
         if (b < FG_BINS && l < ncls) {
             const float* d = stab + (l * FG_BINS + b) * 32 + sub * 4;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) g.v[k] = fg_round<T>(gs * d[k]);
+            for (int k = 0; k < 4; ++k) g.v[k] = round_as<T>(gs * d[k]);
         }
         float ss = v.v[0] * v.v[0] + v.v[1] * v.v[1] + v.v[2] * v.v[2] + v.v[3] * v.v[3];
         float dot = v.v[0] * g.v[0] + v.v[1] * g.v[1] + v.v[2] * g.v[2] + v.v[3] * g.v[3];
@@ -852,16 +849,14 @@ extern "C" int tcct_l2norm_bwd_fplgrad(const void* x, const uint8_t* labels, con
     TCCT_CHECK(ncls >= 1 && ncls <= 16 && labels && binmap && dpro_over_n, "l2norm_bwd_fplgrad: bad arguments (ncls=%d)", ncls);
     const size_t lds = sizeof(float) * (size_t)ncls * FG_BINS * 32;
     TCCT_DISPATCH(dtype, {
-        static bool at_ = false;
-        if (!at_) { (void)hipFuncSetAttribute((const void*)k_l2norm_bwd_fplgrad<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); at_ = true; }
-        hipLaunchKernelGGL((k_l2norm_bwd_fplgrad<T>), dim3(tcct_grid(M * 8, PB, 2048)), dim3(PB), lds, (hipStream_t)stream, (const T*)x, labels, binmap,
-                           dpro_over_n, grad_out, grad_scale, ncls, (const T*)res, (T*)dx, M, eps, scale); });
+        tcct_launch<k_l2norm_bwd_fplgrad<T>, 80 * 1024>(dim3(tcct_grid(M * 8, PB, 2048)), dim3(PB), lds, (hipStream_t)stream, (const T*)x, labels, binmap,
+                                                        dpro_over_n, grad_out, grad_scale, ncls, (const T*)res, (T*)dx, M, eps, scale); });
     TCCT_LAUNCH_OK();
 }
 
 // dx [N,H,W,32] = bilinear_bwd(dfeat [N,Ho,Wo,32]) with dfeat looked up: k_bilinear_bwd_tab with the contributor loads replaced by LDS reads.  Per tile
 // the (label, bin) bytes of the contributing output region (a contiguous rectangle: the contributors of neighbouring inputs overlap) are read ONCE,
-// coalesced, and kept as 16-bit row ids; the table is stored pre-scaled and pre-rounded (fg_round(g * dpro)), so the inner loop is two LDS reads and
+// coalesced, and kept as 16-bit row ids; the table is stored pre-scaled and pre-rounded (round_as(g * dpro)), so the inner loop is two LDS reads and
 // eight FMAs per contributor.  (First version: two global byte loads per contributor and item, four items per pixel: 0.38 ms for the two calls of
 // the bench step, as slow as the dense gather it replaced.)
 template <typename T>
@@ -878,7 +873,7 @@ __global__ void __launch_bounds__(PB) k_bilinear_bwd_fplgrad(const uint8_t* __re
     __shared__ int s_org[4];                    // first row / column of the contributing region and its extent
     const int t = threadIdx.x;
     const float gs = gscale * (gout ? *gout : 1.f);
-    for (int i = t; i < ncls * FG_BINS * 32; i += PB) stab[i] = fg_round<T>(gs * dpro[i]);
+    for (int i = t; i < ncls * FG_BINS * 32; i += PB) stab[i] = round_as<T>(gs * dpro[i]);
     int bid = blockIdx.x;
     const int tw = bid % tilesW; bid /= tilesW;
     const int th = bid % tilesH;
@@ -971,10 +966,8 @@ extern "C" int tcct_bilinear_bwd_fplgrad(const uint8_t* labels, const uint8_t* b
                        sizeof(uint16_t) * (size_t)RMAX * CMAX;
     TCCT_CHECK(lds <= 150 * 1024, "bilinear_bwd_fplgrad: %zu B of LDS", lds);
     TCCT_DISPATCH(dtype, {
-        static bool at_ = false;
-        if (!at_) { (void)hipFuncSetAttribute((const void*)k_bilinear_bwd_fplgrad<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); at_ = true; }
-        hipLaunchKernelGGL((k_bilinear_bwd_fplgrad<T>), dim3((unsigned)blocks), dim3(PB), lds, (hipStream_t)stream, labels, binmap, dpro_over_n, grad_out,
-                           grad_scale, ncls, (T*)dx, N, H, W, Ho, Wo, sh, sw, align_corners, DW, KT, tilesW, tilesH, RMAX, CMAX); });
+        tcct_launch<k_bilinear_bwd_fplgrad<T>, 150 * 1024>(dim3((unsigned)blocks), dim3(PB), lds, (hipStream_t)stream, labels, binmap, dpro_over_n, grad_out,
+                                                           grad_scale, ncls, (T*)dx, N, H, W, Ho, Wo, sh, sw, align_corners, DW, KT, tilesW, tilesH, RMAX, CMAX); });
     TCCT_LAUNCH_OK();
 }
 

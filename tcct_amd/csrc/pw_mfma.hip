@@ -14,7 +14,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int u32x4;
 
 #define PWB 256
 
@@ -27,8 +26,6 @@ __device__ __forceinline__ void st_out4(float* p, float a, float b, float c, flo
 }
 
 // NT = number of 32-channel output tiles handled per block (N chunk = NT*32 starting at blockIdx.y*NT*32)
-__device__ __forceinline__ float rnd_out(float v, const bf16*) { return __bfloat162float(__float2bfloat16(v)); }
-__device__ __forceinline__ float rnd_out(float v, const float*) { return v; }
 
 // Concatenation-free operands (MHCA_stage.aggregate, reference nets/tcct.py:600-616: `cat([InvRes(x), Encoder(x)], 1)` -> 1x1 conv): the
 // input rows may live in TWO tensors (channels [0,K1) in x, [K1,K) in x2) and, for the input-gradient GEMM, the output rows may go
@@ -338,18 +335,31 @@ static int pw_fwd_impl(const void* x, const float* w, const float* bias, void* y
                        int out_dtype, double* stats, int stat_pre, tcct_stream_t stream, const float* aff = nullptr, int aff_pre = 0,
                        int aff_post = 0, PwSplit sp = PwSplit{nullptr, 0, nullptr, 0, nullptr, nullptr, 1, nullptr});
 struct PwRes { const bf16* res; const float* rscale; int64_t per_sample; bf16* yplain; const float* xab; const float* aff; int aff_post; int has_aff; };
-static bool pw_fwd2_ok(int64_t M, int K, int N, int K1, bool has_x2);
-// shapes of the tile-staged forward WITH the inference epilogue: square 64 / 96 / 128 (plain or with the residual), the concatenated 64 + 64 -> 96
-static bool pw_fwd2_aff_ok(int64_t M, int K, int N, bool has_x2, bool has_res) {
-    if (M * (int64_t)(K > N ? K : N) * 2 >= (1LL << 31)) return false;
-    if (has_x2) return K == 128 && N == 96 && !has_res;
-    return K == N && (K == 64 || K == 96 || K == 128);
+// The kernel's PwRes argument, one builder per use.  Training: y = res + rscale[m / per_sample] * (x W^T + bias), yplain also receives the product (all nullable: no residual)
+static PwRes pw_res_train(const bf16* res, const float* rscale, int64_t per_sample, bf16* yplain) {
+    PwRes r{};
+    r.res = res; r.rscale = rscale; r.per_sample = per_sample; r.yplain = yplain;
+    return r;
 }
+// training, x = hswish(a_prev y_prev + b_prev) applied while the tile is staged: xab = {a[K], b[K]}
+static PwRes pw_res_xaff(const float* ab_prev) {
+    PwRes r{};
+    r.per_sample = 1; r.xab = ab_prev;
+    return r;
+}
+// inference epilogue y = [res +] act(aff_post, a[c] (x W^T + bias[c]) + b[c]), aff = {a[N], b[N]} (NULL: a = 1, b = 0: has_aff is the switch); xab (nullable) as above
+static PwRes pw_res_affine(const bf16* res, const float* xab, const float* aff, int aff_post) {
+    PwRes r{};
+    r.res = res; r.per_sample = 1; r.xab = xab; r.aff = aff; r.aff_post = aff_post; r.has_aff = 1;
+    return r;
+}
+// The VARIANT of k_pw_fwd2 beyond what the operands say (stats / x2 / res / aff present or not): gelu on load, the activation of the BatchNorm in front (with PwRes.xab)
+struct PwFwd2Mode { bool gelu_x = false; int xap = -1; };
+static bool pw_fwd2_ok(int64_t M, int K, int N, int K1, bool has_x2);
+// shapes of the tile-staged forward WITH the inference epilogue (read from pw_fwd2_table): square 64 / 96 / 128 (plain or with the residual), the concatenated 64 + 64 -> 96
+static bool pw_fwd2_aff_ok(int64_t M, int K, int N, bool has_x2, bool has_res);
 static int pw_fwd2_launch(const void* x, const void* x2, const float* w, const float* bias, void* y, int64_t M, int K, int N, double* stats,
-                          int stat_pre, tcct_stream_t stream, PwRes pr, bool gelu_x = false);
-struct PwRes;
-static int pw_fwd2_route(const void* x, const void* x2, const float* w, const float* bias, void* y, int64_t M, int K, int N, double* stats,
-                         int stat_pre, tcct_stream_t stream, const bf16* res, const float* rscale, int64_t per_sample, bf16* yplain);
+                          int stat_pre, tcct_stream_t stream, PwRes pr, const PwFwd2Mode& md = PwFwd2Mode());
 static bool pw_fwd2_enabled() {         // compile-time A/B switch (off: the direct-from-global forward kernel for every shape)
     static int on = -1;
     if (on < 0) on = 1;
@@ -424,7 +434,7 @@ extern "C" int tcct_pw_fwd_affine(const void* x, const float* w, const float* bi
 extern "C" int tcct_pw_fwd_affine_residual(const void* x, const float* w, const float* bias, const float* ab, const void* res, void* y, int64_t M, int K, int N,
                                            tcct_stream_t stream) {
     TCCT_CHECK(res != nullptr && pw_fwd2_aff_ok(M, K, N, false, true), "pw_fwd_affine_residual: K=%d N=%d unsupported (64, 96 or 128 square) or res NULL", K, N);
-    return pw_fwd2_launch(x, nullptr, w, bias, y, M, K, N, nullptr, 0, stream, PwRes{(const bf16*)res, nullptr, 1, nullptr, nullptr, ab, TCCT_ACT_NONE, 1});
+    return pw_fwd2_launch(x, nullptr, w, bias, y, M, K, N, nullptr, 0, stream, pw_res_affine((const bf16*)res, nullptr, ab, TCCT_ACT_NONE));
 }
 /* inference: y = res + (a[c] * (hswish(a_prev[k] * y_prev + b_prev[k]) W^T + bias[c]) + b[c]): the InvRes tail `x + BN(conv2(hswish(BN(dw))))` (nets/tcct.py:563-572) as ONE
  * GEMM over the depthwise convolution's raw output -- `norm`'s eval-mode BatchNorm + Hardswish applied while the tile is staged, conv2's BatchNorm and the residual in the
@@ -432,23 +442,25 @@ extern "C" int tcct_pw_fwd_affine_residual(const void* x, const float* w, const 
 extern "C" int tcct_pw_fwd_xaff_affine_residual(const void* y_prev, const float* ab_prev, const float* w, const float* bias, const float* ab, const void* res, void* y,
                                                 int64_t M, int K, int N, tcct_stream_t stream) {
     TCCT_CHECK(y_prev && ab_prev && res != nullptr && pw_fwd2_aff_ok(M, K, N, false, true), "pw_fwd_xaff_affine_residual: K=%d N=%d unsupported (64, 96 or 128 square) or NULL argument", K, N);
-    return pw_fwd2_launch(y_prev, nullptr, w, bias, y, M, K, N, nullptr, 0, stream, PwRes{(const bf16*)res, nullptr, 1, nullptr, ab_prev, ab, TCCT_ACT_NONE, 1});
+    PwFwd2Mode md;
+    md.xap = TCCT_ACT_HSWISH;
+    return pw_fwd2_launch(y_prev, nullptr, w, bias, y, M, K, N, nullptr, 0, stream, pw_res_affine((const bf16*)res, ab_prev, ab, TCCT_ACT_NONE), md);
 }
 /* inference: y = post_act(a[c] * ([x1 | x2] W^T + bias[c]) + b[c]) over the never-materialised concatenation of two 64-channel tensors, N = 96: `aggregate` of MHCA stage 0
  * (nets/tcct.py:600-616) with its eval-mode BatchNorm + Hardswish in the epilogue */
 extern "C" int tcct_pw_fwd_cat2_affine(const void* x1, const void* x2, const float* w, const float* bias, const float* ab, int post_act, void* y, int64_t M, int K, int N,
                                        tcct_stream_t stream) {
     TCCT_CHECK(x2 != nullptr && pw_fwd2_aff_ok(M, K, N, true, false), "pw_fwd_cat2_affine: K=%d N=%d unsupported (64 + 64 -> 96)", K, N);
-    return pw_fwd2_launch(x1, x2, w, bias, y, M, K, N, nullptr, 0, stream, PwRes{nullptr, nullptr, 1, nullptr, nullptr, ab, post_act, 1});
+    return pw_fwd2_launch(x1, x2, w, bias, y, M, K, N, nullptr, 0, stream, pw_res_affine(nullptr, nullptr, ab, post_act));
 }
 static int pw_fwd_impl(const void* x, const float* w, const float* bias, void* y, int64_t M, int K, int N, int transposed,
                        int out_dtype, double* stats, int stat_pre, tcct_stream_t stream, const float* aff, int aff_pre, int aff_post, PwSplit sp) {
     if (!transposed && out_dtype == TCCT_BF16 && (aff || aff_post) && !aff_pre && !stats && !sp.y2 && !sp.yplain && !sp.rscale && pw_fwd2_enabled()
         && pw_fwd2_aff_ok(M, K, N, sp.x2 != nullptr, sp.res != nullptr) && (!sp.x2 || sp.K1 == 64))
-        return pw_fwd2_launch(x, sp.x2, w, bias, y, M, K, N, nullptr, 0, stream, PwRes{sp.res, nullptr, 1, nullptr, nullptr, aff, aff_post, 1});
+        return pw_fwd2_launch(x, sp.x2, w, bias, y, M, K, N, nullptr, 0, stream, pw_res_affine(sp.res, nullptr, aff, aff_post));
     if (!transposed && out_dtype == TCCT_BF16 && !aff && !aff_pre && !aff_post && !sp.y2 && pw_fwd2_enabled()
         && pw_fwd2_ok(M, K, N, sp.K1, sp.x2 != nullptr) && (!stats || N <= 128) && !(sp.res && (sp.x2 || stats)))
-        return pw_fwd2_route(x, sp.x2, w, bias, y, M, K, N, stats, stat_pre, stream, sp.res, sp.rscale, sp.per_sample, sp.yplain);
+        return pw_fwd2_launch(x, sp.x2, w, bias, y, M, K, N, stats, stat_pre, stream, pw_res_train(sp.res, sp.rscale, sp.per_sample, sp.yplain));
     if (sp.x2) TCCT_CHECK(sp.K1 % 32 == 0 && sp.K1 > 0 && sp.K1 < K, "pw_fwd_cat2: K1=%d must be a multiple of 32 inside (0, K)", sp.K1);
     if (sp.y2) TCCT_CHECK(sp.N1 % 32 == 0 && sp.N1 > 0 && sp.N1 < N && N % 32 == 0 && out_dtype == TCCT_BF16, "pw_dgrad_split2: N1=%d must be a multiple of 32 inside (0, N), bf16 output", sp.N1);
     TCCT_CHECK(K % 32 == 0 && K >= 32 && K <= 512, "pw_fwd: K=%d must be a multiple of 32 (<=512)", K);
@@ -478,35 +490,22 @@ static int pw_fwd_impl(const void* x, const float* w, const float* bias, void* y
     const int cap = 256 * per_cu;
     if (gx > cap) gx = cap;
     hipStream_t st = (hipStream_t)stream;
-#define PW_L(NTV, TO)                                                                                                        \
-    do {                                                                                                                     \
-        static bool attr = false;                                                                                            \
-        if (!attr) { (void)hipFuncSetAttribute((const void*)k_pw_fwd<NTV, TO, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; } \
-        hipLaunchKernelGGL((k_pw_fwd<NTV, TO, false, false>), dim3((unsigned)gx, gy), dim3(PWB), lds, st, (const bf16*)x, w, bias, (TO*)y, M, K, N, transposed, nullptr, 0, aff, aff_pre, aff_post, sp); \
-    } while (0)
-#define PW_D(TO)                                                                  \
-    switch (NT) {                                                                 \
-        case 1: PW_L(1, TO); break; case 2: PW_L(2, TO); break; case 3: PW_L(3, TO); break; \
-        case 4: PW_L(4, TO); break; default: PW_L(5, TO); break;                  \
-    }
+    // one kernel per (N-tiles per block, output type, epilogue); the statistics epilogue exists for 1-4 N-tiles (see above)
+#define PW_GO(NTV, TO, ST, AF) tcct_launch<k_pw_fwd<NTV, TO, ST, AF>, 160 * 1024>(dim3((unsigned)gx, gy), dim3(PWB), lds, st, (const bf16*)x, w, bias, (TO*)y, M, K, N, transposed, \
+                                                                                stats, stats ? stat_pre : 0, aff, aff_pre, aff_post, sp)
+#define PW_NT4(TO, ST, AF) case 1: PW_GO(1, TO, ST, AF); break; case 2: PW_GO(2, TO, ST, AF); break; case 3: PW_GO(3, TO, ST, AF); break; case 4: PW_GO(4, TO, ST, AF); break
+    bool hit = true;
     if (aff || aff_pre || aff_post || sp.res) {       // inference / residual epilogue: separate instantiations, the training kernels stay as they are
         TCCT_CHECK(out_dtype == TCCT_BF16 && !stats, "pw_fwd_affine: bf16 output only");
-#define PW_A(NTV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd<NTV, bf16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd<NTV, bf16, false, true>), dim3((unsigned)gx, gy), dim3(PWB), lds, st, (const bf16*)x, w, bias, (bf16*)y, M, K, N, transposed, nullptr, 0, aff, aff_pre, aff_post, sp); }
-        if (NT == 1) PW_A(1) else if (NT == 2) PW_A(2) else if (NT == 3) PW_A(3) else if (NT == 4) PW_A(4) else PW_A(5)
-#undef PW_A
+        switch (NT) { PW_NT4(bf16, false, true); case 5: PW_GO(5, bf16, false, true); break; default: hit = false; }
     }
-    else if (stats) {
-#define PW_S(NTV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd<NTV, bf16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd<NTV, bf16, true, false>), dim3((unsigned)gx, gy), dim3(PWB), lds, st, (const bf16*)x, w, bias, (bf16*)y, M, K, N, transposed, stats, stat_pre, nullptr, 0, 0, sp); }
-        if (NT == 1) PW_S(1) else if (NT == 2) PW_S(2) else if (NT == 3) PW_S(3) else PW_S(4)
-#undef PW_S
-    }
-    else if (out_dtype == TCCT_BF16) { PW_D(bf16); }
-    else if (out_dtype == TCCT_F32) { PW_D(float); }
+    else if (stats) switch (NT) { PW_NT4(bf16, true, false); default: hit = false; }
+    else if (out_dtype == TCCT_BF16) switch (NT) { PW_NT4(bf16, false, false); case 5: PW_GO(5, bf16, false, false); break; default: hit = false; }
+    else if (out_dtype == TCCT_F32) switch (NT) { PW_NT4(float, false, false); case 5: PW_GO(5, float, false, false); break; default: hit = false; }
     else { tcct_set_error("pw_fwd: bad out dtype"); return -1; }
-#undef PW_D
-#undef PW_L
+#undef PW_NT4
+#undef PW_GO
+    TCCT_CHECK(hit, "pw_fwd: no kernel for %d N-tiles per block (stats %d)", NT, stats != nullptr);
     TCCT_LAUNCH_OK();
 }
 
@@ -775,7 +774,6 @@ static int pw_wgrad_impl(const void* x, const void* x2, int K1, const void* dy, 
     size_t red = (size_t)NT * 32 * KTB * 32 * 4;
     if (red > lds) lds = red;
     const int64_t tiles = (M + PW_P - 1) / PW_P;
-    (void)hipFuncSetAttribute;
     int per_cu = (int)((160 * 1024) / (lds + 512));
     if (per_cu > 2) per_cu = 2;                                   // __launch_bounds__(256, 2)
     if (per_cu < 1) per_cu = 1;
@@ -786,8 +784,8 @@ static int pw_wgrad_impl(const void* x, const void* x2, int K1, const void* dy, 
     if (tiles <= 1024) { int small = 128 / gy; if (small < 16) small = 16; if (gx > small) gx = small; }
     if (gx > tiles) gx = (int)tiles;
     if (gx < 1) gx = 1;
-#define WL(NTV, KV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_wgrad<NTV, KV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } } hipLaunchKernelGGL((k_pw_wgrad<NTV, KV>), dim3(gx, gy), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, dw, dbias, M, K, N, SX, SD, (const bf16*)x2, K1, ldy)
-    if (KTB == 2) { switch (NT) { case 1: WL(1, 2); break; default: WL(2, 2); break; } }
+#define WL(NTV, KV) tcct_launch<k_pw_wgrad<NTV, KV>, 160 * 1024>(dim3(gx, gy), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, dw, dbias, M, K, N, SX, SD, (const bf16*)x2, K1, ldy, C3Geom{})
+    if (KTB == 2) { switch (NT) { case 1: WL(1, 2); break; default: WL(2, 2); break; } }      // (KTB == 2 only with NT <= 2, N <= 160 checked above)
     else { switch (NT) { case 1: WL(1, 1); break; case 2: WL(2, 1); break; case 3: WL(3, 1); break; case 4: WL(4, 1); break; default: WL(5, 1); break; } }
 #undef WL
     TCCT_LAUNCH_OK();
@@ -1311,23 +1309,125 @@ k_pw_bwd(const bf16* __restrict__ x, const bf16* __restrict__ dy, const float* _
     }
 }
 
+// ------------------------------------------------------------------------------------------------ host side of k_pw_bwd
+// The VARIANT of k_pw_bwd an entry asks for (its template arguments behind NT / KT, which follow from the shape), apart from the operands.
+struct PwBwdMode { bool split = false; int bnp = -1, redp = -1; bool gelu_x = false; int xap = -1; bool lnb = false, dy2 = false; };
+// The kernel's PwBnBwd argument, one builder per use: its fields carry different operands in the different forms, and here is where that is decided.
+// BatchNorm behind the convolution with the constants precomputed (coef [5][N], tcct_bn_bwd_coef); y_prev / ab_prev / sums_prev (nullable): the BatchNorm in front (REDP)
+static PwBnBwd pw_bn_coef(const void* y, const float* coef, const void* y_prev, const float* ab_prev, double* sums_prev) {
+    PwBnBwd b{};
+    b.y = (const bf16*)y; b.coef = coef; b.yprev = (const bf16*)y_prev; b.abprev = ab_prev; b.sums_prev = sums_prev;
+    return b;
+}
+// ... with the constants derived in the kernel from the batch sums: coef stays NULL, which is the kernel's switch
+static PwBnBwd pw_bn_sums(const void* y, const double* sums, int raw, const float* mean_rstd, const float* ab, float* dgamma, float* dbeta, const void* y_prev,
+                          const float* ab_prev, double* sums_prev) {
+    PwBnBwd b = pw_bn_coef(y, nullptr, y_prev, ab_prev, sums_prev);
+    b.sums = sums; b.raw = raw; b.mean_rstd = mean_rstd; b.ab = ab; b.dgamma = dgamma; b.dbeta = dbeta;
+    return b;
+}
+// LayerNorm in front (LNB): yprev carries the LayerNorm's input t, abprev its gamma, mean_rstd its saved per-row statistics [M][2], dgamma / dbeta are the LayerNorm's
+static PwBnBwd pw_bn_ln_front(const void* t, const float* gamma, const float* mean_rstd, float* dgamma, float* dbeta) {
+    PwBnBwd b{};
+    b.yprev = (const bf16*)t; b.abprev = gamma; b.mean_rstd = mean_rstd; b.dgamma = dgamma; b.dbeta = dbeta;
+    return b;
+}
+// second output gradient (DY2): y carries dy_b
+static PwBnBwd pw_bn_dy2(const void* dy_b) {
+    PwBnBwd b{};
+    b.y = (const bf16*)dy_b;
+    return b;
+}
+
+// THE list of k_pw_bwd kernels: a row is the template arguments and the launcher of exactly that instantiation.  A form is added by adding its row (every row costs
+// about a minute of hipcc); a combination without a row is an error (pw_bwd_impl), never a neighbouring kernel, and tcct_pw_bwd_bn_supported answers from here.
+// Why rows are absent -- the register budget (256 VGPRs at two blocks per CU): the reduction epilogue (REDP) keeps 16 partial sums + 8 prefetched registers per 32
+// input channels, which only fits at K = N = 64 (the concatenated 128 -> 96 form spills 51 VGPRs with it, 96 / 128 square 94 / 215); the plain BatchNorm form (BNP)
+// spills 37 VGPRs at 128 x 128 and measured SLOWER than the separate kernels there (0.080 vs 0.045 + 0.02 ms at level 3); the GELU form spills 30 VGPRs at 128.
+typedef void (*PwBwdLaunch)(dim3, dim3, size_t, hipStream_t, const bf16*, const bf16*, const float*, const bf16*, bf16*, bf16*, float*, float*, int64_t, PwBnBwd);
+struct PwBwdRow { int nt, kt; bool split; int bnp, redp; bool gx; int xap; bool lnb, dy2; PwBwdLaunch launch; };
+static_assert(TCCT_ACT_HSWISH == 2 && TCCT_ACT_NONE == 0, "activation codes are template arguments below");
+#define PWB_ROW(NT, KT, SP, BN, RD, GX, XA, LN, D2) {NT, KT, SP, BN, RD, GX, XA, LN, D2, tcct_launch<k_pw_bwd<NT, KT, SP, BN, RD, GX, XA, LN, D2>, 160 * 1024>}
+#define PWB_PLAIN(NT, KT, SP) PWB_ROW(NT, KT, SP, -1, -1, false, -1, false, false)
+#define PWB_BN(NT, KT, SP, BN, RD) PWB_ROW(NT, KT, SP, BN, RD, false, -1, false, false)
+static const PwBwdRow pw_bwd_table[] = {
+    // plain (dx = dy W + res): every K x N of 32 .. 128
+    PWB_PLAIN(1, 1, false), PWB_PLAIN(1, 2, false), PWB_PLAIN(1, 3, false), PWB_PLAIN(1, 4, false),
+    PWB_PLAIN(2, 1, false), PWB_PLAIN(2, 2, false), PWB_PLAIN(2, 3, false), PWB_PLAIN(2, 4, false),
+    PWB_PLAIN(3, 1, false), PWB_PLAIN(3, 2, false), PWB_PLAIN(3, 3, false), PWB_PLAIN(3, 4, false),
+    PWB_PLAIN(4, 1, false), PWB_PLAIN(4, 2, false), PWB_PLAIN(4, 3, false), PWB_PLAIN(4, 4, false),
+    // concatenated x = [x1 | x2]: two halves of 64 channels, or of 32 into 32 outputs (the decoder's composed tail)
+    PWB_PLAIN(1, 4, true), PWB_PLAIN(2, 4, true), PWB_PLAIN(3, 4, true), PWB_PLAIN(4, 4, true), PWB_PLAIN(1, 2, true),
+    // BatchNorm behind (BNP = its activation): 32 outputs without activation, 64 / 96 square, the concatenated 128 -> 96 with Hardswish
+    PWB_BN(1, 1, false, 0, -1), PWB_BN(1, 3, false, 0, -1), PWB_BN(1, 4, false, 0, -1),
+    PWB_BN(2, 2, false, 0, -1), PWB_BN(2, 2, false, 2, -1), PWB_BN(3, 3, false, 0, -1), PWB_BN(3, 3, false, 2, -1), PWB_BN(3, 4, true, 2, -1),
+    // ... and the batch sums of the BatchNorm in front in the dx epilogue (REDP = its activation): 64 square only
+    PWB_BN(2, 2, false, 0, 0), PWB_BN(2, 2, false, 0, 2), PWB_BN(2, 2, false, 2, 0), PWB_BN(2, 2, false, 2, 2),
+    // x = hswish(a y_prev + b) applied on load (InvRes.norm -> conv2), BatchNorm behind without activation; 64: with the reduction epilogue
+    PWB_ROW(2, 2, false, 0, 2, false, 2, false, false), PWB_ROW(3, 3, false, 0, -1, false, 2, false, false),
+    // x = gelu(x1) applied on load (Mlp.fc1 -> fc2)
+    PWB_ROW(2, 2, false, -1, -1, true, -1, false, false), PWB_ROW(3, 3, false, -1, -1, true, -1, false, false),
+    // fc1 behind MHCABlock.norm2: the LayerNorm backward in the dx epilogue
+    PWB_ROW(2, 2, false, -1, -1, false, -1, true, false),
+    // decoder block tail: the two output gradients summed on load
+    PWB_ROW(1, 1, false, -1, -1, false, -1, false, true),
+};
+#undef PWB_BN
+#undef PWB_PLAIN
+#undef PWB_ROW
+static const PwBwdRow* pw_bwd_find(int K, int N, const PwBwdMode& md) {
+    if (K % 32 || N % 32) return nullptr;
+    for (const PwBwdRow& r : pw_bwd_table)
+        if (r.nt == N / 32 && r.kt == K / 32 && r.split == md.split && r.bnp == md.bnp && r.redp == md.redp && r.gx == md.gelu_x && r.xap == md.xap && r.lnb == md.lnb &&
+            r.dy2 == md.dy2) return &r;
+    return nullptr;
+}
+
 /* Fused backward of y = x W^T + b for bf16 rows: dx [M,K] (= dy W, + res when res != NULL), dw [N,K] fp32 and dbias [N] fp32 (nullable)
- * are ACCUMULATED into after being cleared here (or by the caller: tcct_set_outputs_prezeroed).  K, N in {32, 64, 96, 128}. */
+ * are ACCUMULATED into after being cleared here (or by the caller: tcct_set_outputs_prezeroed), and so are the sums of a reduction epilogue (bn.sums_prev) and the
+ * LayerNorm's dgamma / dbeta.  Nothing touches the device before the kernel is found. */
 static int pw_bwd_impl(const void* x, const void* dy, const float* w, const void* res, void* dx, void* dx_plain, float* dw, float* dbias,
-                       int64_t M, int K, int N, tcct_stream_t stream, bool split = false, int bnp = -1, int redp = -1,
-                       PwBnBwd bn = PwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr}, bool gelu_x = false,
-                       int xap = -1, bool lnb = false, bool dy2 = false);
+                       int64_t M, int K, int N, tcct_stream_t stream, const PwBwdMode& md = PwBwdMode(), PwBnBwd bn = PwBnBwd{}) {
+    const PwBwdRow* row = pw_bwd_find(K, N, md);
+    TCCT_CHECK(row != nullptr, "pw_bwd: K=%d N=%d unsupported: no kernel for NT=%d KT=%d SPLIT=%d BNP=%d REDP=%d GX=%d XAP=%d LNB=%d DY2=%d", K, N, N / 32, K / 32,
+               (int)md.split, md.bnp, md.redp, (int)md.gelu_x, md.xap, (int)md.lnb, (int)md.dy2);
+    TCCT_CHECK(M > 0 && M * (int64_t)(K > N ? K : N) * 2 < (1LL << 31), "pw_bwd: tensor exceeds the 2 GiB buffer-descriptor range");
+    const int NT = N / 32, KT = K / 32;
+    const int SX = 64 * KT + ((KT & 1) ? 0 : 64), SD = 64 * NT + ((NT & 1) ? 0 : 64), SW = 2 * N + 16;
+    const size_t lds = (size_t)PB_P * (SX + SD) + (((size_t)K * SW + 15) & ~(size_t)15) + 4 * 2560 + (md.bnp >= 0 ? (size_t)5 * N * 4 : 0) +
+                       ((md.redp >= 0 || md.xap >= 0 || md.lnb) ? (size_t)2 * K * 4 : 0);
+    TCCT_CHECK(lds <= 160 * 1024, "pw_bwd: %zu B of LDS", lds);
+    hipStream_t st = (hipStream_t)stream;
+    if (!tcct_skip_zero_fill()) {
+        bool ok = true;
+        if (md.redp >= 0) ok = ok && hipMemsetAsync(bn.sums_prev, 0, sizeof(double) * 2 * (md.split ? K / 2 : K), st) == hipSuccess;
+        if (md.lnb) ok = ok && hipMemsetAsync(bn.dgamma, 0, sizeof(float) * K, st) == hipSuccess && hipMemsetAsync(bn.dbeta, 0, sizeof(float) * K, st) == hipSuccess;
+        ok = ok && hipMemsetAsync(dw, 0, sizeof(float) * (size_t)N * K, st) == hipSuccess;
+        if (dbias) ok = ok && hipMemsetAsync(dbias, 0, sizeof(float) * N, st) == hipSuccess;
+        if (!ok) { tcct_set_error("pw_bwd: memset failed"); return -2; }
+    }
+    const int64_t tiles = (M + PB_P - 1) / PB_P;
+    int per_cu = (int)((160 * 1024) / (lds + 256));
+    if (per_cu > 2) per_cu = 2;
+    // (one block per CU looked better in tools/kbench.py -- 64->64 @L1 0.135 -> 0.125 ms, 32->32 @L0 0.258 -> 0.235 -- but inside the training
+    // step, where the tensors are not the same two buffers over and over, it was slower: k_pw_bwd 2.46 -> 2.57 ms per step; two per CU stay)
+    int64_t gx = 256 * per_cu;
+    if (gx > tiles) gx = tiles;
+    row->launch(dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, w, (const bf16*)res, (bf16*)dx, (bf16*)dx_plain, dw, dbias, M, bn);
+    TCCT_LAUNCH_OK();
+}
+static PwBwdMode pw_bwd_split() { PwBwdMode md; md.split = true; return md; }
 /* the same over a concatenation: x = [x1 | x2], dx = [dx1 | dx2], each [M, K/2] (K = 128): backward of tcct_pw_fwd_cat2 */
 extern "C" int tcct_pw_bwd_cat2(const void* x1, const void* x2, const void* dy, const float* w, void* dx1, void* dx2, float* dw, int64_t M,
                                 int K, int N, tcct_stream_t stream) {
     TCCT_CHECK(K == 128 && x2 != nullptr && dx2 != nullptr, "pw_bwd_cat2: two halves of 64 channels only (K=%d)", K);
-    return pw_bwd_impl(x1, dy, w, x2, dx1, dx2, dw, nullptr, M, K, N, stream, true);
+    return pw_bwd_impl(x1, dy, w, x2, dx1, dx2, dw, nullptr, M, K, N, stream, pw_bwd_split());
 }
 /* the concatenated form with a bias gradient and two halves of 32 OR 64 channels (K = 64 / 128): the decoder's composed tail, tcct_tail_compose */
 extern "C" int tcct_pw_bwd_cat2_bias(const void* x1, const void* x2, const void* dy, const float* w, void* dx1, void* dx2, float* dw, float* dbias,
                                      int64_t M, int K, int N, tcct_stream_t stream) {
-    TCCT_CHECK((K == 128 || (K == 64 && N == 32)) && x2 != nullptr && dx2 != nullptr, "pw_bwd_cat2_bias: K=%d N=%d (128 -> any, or 64 -> 32)", K, N);
-    return pw_bwd_impl(x1, dy, w, x2, dx1, dx2, dw, dbias, M, K, N, stream, true);
+    TCCT_CHECK(x2 != nullptr && dx2 != nullptr, "pw_bwd_cat2_bias: x2 or dx2 is NULL (K=%d N=%d: 128 -> any, or 64 -> 32)", K, N);
+    return pw_bwd_impl(x1, dy, w, x2, dx1, dx2, dw, dbias, M, K, N, stream, pw_bwd_split());
 }
 extern "C" int tcct_pw_bwd(const void* x, const void* dy, const float* w, const void* res, void* dx, float* dw, float* dbias, int64_t M,
                            int K, int N, tcct_stream_t stream) {
@@ -1340,20 +1440,13 @@ extern "C" int tcct_pw_bwd_residual2(const void* x, const void* dy, const float*
     TCCT_CHECK(res != nullptr && dx_plain != nullptr && dx_plain != dx_sum, "pw_bwd_residual2: needs res and two distinct outputs");
     return pw_bwd_impl(x, dy, w, res, dx_sum, dx_plain, dw, dbias, M, K, N, stream);
 }
-/* Shapes / activation kinds for which tcct_pw_bwd_bn has a kernel (the host mirror asks before building its autograd node):
+/* Shapes / activation kinds for which tcct_pw_bwd_bn has a kernel (the host mirror asks before building its autograd node), read from pw_bwd_table:
  *   post (BatchNorm behind the convolution) and red_post (BatchNorm in front of it, -1: no reduction epilogue): TCCT_ACT_NONE / TCCT_ACT_HSWISH;
  *   K = N in {64, 96} (the reduction epilogue only at 64); N = 32 with K in {32, 96, 128} and the concatenated K = 128 -> N = 96 form without it. */
 extern "C" int64_t tcct_pw_bwd_bn_supported(int K, int N, int post, int red_post, int split) {
-    const bool p_ok = post == TCCT_ACT_NONE || post == TCCT_ACT_HSWISH;
-    const bool r_ok = red_post == -1 || red_post == TCCT_ACT_NONE || red_post == TCCT_ACT_HSWISH;
-    if (!p_ok || !r_ok) return 0;
-    // Register budget (256 VGPRs at two blocks per CU): the reduction epilogue keeps 16 partial sums + 8 prefetched registers per 32 input
-    // channels, which only fits at K = N = 64 (the concatenated 128 -> 96 form spills 51 VGPRs with it, 96 / 128 square 94 / 215); the plain
-    // form spills 37 VGPRs at 128 x 128 and measured SLOWER than the separate kernels there (0.080 vs 0.045 + 0.02 ms at level 3): not offered.
-    if (split) return K == 128 && N == 96 && post == TCCT_ACT_HSWISH && red_post == -1;
-    if (K == N && (K == 64 || K == 96)) return red_post == -1 || K == 64;
-    if (N == 32 && (K == 32 || K == 96 || K == 128)) return red_post == -1 && post == TCCT_ACT_NONE;
-    return 0;
+    PwBwdMode md;
+    md.split = split != 0; md.bnp = post; md.redp = red_post;
+    return post >= 0 && pw_bwd_find(K, N, md) != nullptr;
 }
 /* Backward of  z = post(BN_train(x W^T + bias)) [+ residual]  given dz (the gradient of z), in ONE pass over dz and y:
  *   dy_conv is rebuilt from (dz, y, coef) while the tiles are staged (coef [5][N] from tcct_bn_bwd_coef), then dx = dy_conv W (+ res),
@@ -1361,13 +1454,20 @@ extern "C" int64_t tcct_pw_bwd_bn_supported(int K, int N, int post, int red_post
  *   red_post >= 0: x = post_prev(BN_prev(y_prev)) and dx (+ res) is the complete gradient of x -- sums_prev [2][K or K/2] (fp64, zero on entry)
  *   receive {sum dz', sum dz' y_prev} of BN_prev's backward (raw form: tcct_bn_bwd_coef(raw = 1) converts), ab_prev = BN_prev's {a[K], b[K]}. */
 static int pw_bwd_bn_impl(const void* x, const void* x2, const void* dz, PwBnBwd bn, int post, const float* w, const void* res, void* dx, void* dx2,
-                          float* dw, float* dbias, int64_t M, int K, int N, int red_post, tcct_stream_t stream);
+                          float* dw, float* dbias, int64_t M, int K, int N, int red_post, tcct_stream_t stream) {
+    PwBwdMode md;
+    md.split = x2 != nullptr; md.bnp = post; md.redp = red_post;
+    TCCT_CHECK(tcct_pw_bwd_bn_supported(K, N, post, red_post, md.split ? 1 : 0), "pw_bwd_bn: K=%d N=%d post=%d red_post=%d split=%d unsupported", K, N, post,
+               red_post, (int)md.split);
+    TCCT_CHECK(bn.y != nullptr && (red_post < 0 || (bn.yprev && bn.abprev && bn.sums_prev)), "pw_bwd_bn: NULL argument");
+    TCCT_CHECK(!md.split || (dx2 != nullptr && res == nullptr), "pw_bwd_bn: the concatenated form takes x2 / dx2 and no residual");
+    return pw_bwd_impl(x, dz, w, md.split ? x2 : res, dx, md.split ? dx2 : nullptr, dw, dbias, M, K, N, stream, md, bn);
+}
 extern "C" int tcct_pw_bwd_bn(const void* x, const void* x2, const void* dz, const void* y, const float* coef, int post, const float* w,
                               const void* res, void* dx, void* dx2, float* dw, float* dbias, int64_t M, int K, int N, const void* y_prev,
                               const float* ab_prev, int red_post, double* sums_prev, tcct_stream_t stream) {
     TCCT_CHECK(coef != nullptr, "pw_bwd_bn: coef is NULL");
-    return pw_bwd_bn_impl(x, x2, dz, PwBnBwd{(const bf16*)y, coef, (const bf16*)y_prev, ab_prev, sums_prev, nullptr, 0, nullptr, nullptr, nullptr, nullptr},
-                          post, w, res, dx, dx2, dw, dbias, M, K, N, red_post, stream);
+    return pw_bwd_bn_impl(x, x2, dz, pw_bn_coef(y, coef, y_prev, ab_prev, sums_prev), post, w, res, dx, dx2, dw, dbias, M, K, N, red_post, stream);
 }
 /* the same with the constants derived in the kernel from the BatchNorm's batch sums (sums [2][N] fp64 from tcct_bn_bwd_reduce, or raw = 1: from a
  * reduction epilogue), mean_rstd / ab as saved by the forward; dgamma / dbeta [N] are written.  One launch instead of tcct_bn_bwd_coef + tcct_pw_bwd_bn. */
@@ -1376,8 +1476,8 @@ extern "C" int tcct_pw_bwd_bn_sums(const void* x, const void* x2, const void* dz
                                    float* dw, float* dbias, int64_t M, int K, int N, const void* y_prev, const float* ab_prev, int red_post,
                                    double* sums_prev, tcct_stream_t stream) {
     TCCT_CHECK(sums && mean_rstd && ab && dgamma && dbeta, "pw_bwd_bn_sums: NULL argument");
-    return pw_bwd_bn_impl(x, x2, dz, PwBnBwd{(const bf16*)y, nullptr, (const bf16*)y_prev, ab_prev, sums_prev, sums, raw, mean_rstd, ab, dgamma, dbeta},
-                          post, w, res, dx, dx2, dw, dbias, M, K, N, red_post, stream);
+    return pw_bwd_bn_impl(x, x2, dz, pw_bn_sums(y, sums, raw, mean_rstd, ab, dgamma, dbeta, y_prev, ab_prev, sums_prev), post, w, res, dx, dx2, dw, dbias, M, K, N,
+                          red_post, stream);
 }
 /* ... with x NOT materialised: `y_prev` is the input of the BatchNorm in front (train mode, Hardswish behind it) and x = hswish(a_prev y_prev + b_prev)
  * is rebuilt while the tiles are staged (ab_prev = {a[K], b[K]}).  K = N = 64: with the reduction epilogue (red_post = TCCT_ACT_HSWISH, sums_prev as
@@ -1385,132 +1485,37 @@ extern "C" int tcct_pw_bwd_bn_sums(const void* x, const void* x2, const void* dz
 extern "C" int tcct_pw_bwd_bn_sums_xaff(const void* y_prev, const float* ab_prev, const void* dz, const void* y, const double* sums, int raw,
                                         const float* mean_rstd, const float* ab, float* dgamma, float* dbeta, const float* w, const void* res, void* dx,
                                         float* dw, float* dbias, int64_t M, int K, int N, int red_post, double* sums_prev, tcct_stream_t stream) {
-    TCCT_CHECK(y_prev && ab_prev && sums && mean_rstd && ab && dgamma && dbeta, "pw_bwd_bn_sums_xaff: NULL argument");
-    TCCT_CHECK(K == N && ((K == 64 && red_post == TCCT_ACT_HSWISH && sums_prev) || (K == 96 && red_post < 0)), "pw_bwd_bn_sums_xaff: K=%d N=%d red_post=%d unsupported", K, N, red_post);
-    if (red_post >= 0 && !tcct_skip_zero_fill() && hipMemsetAsync(sums_prev, 0, sizeof(double) * 2 * K, (hipStream_t)stream) != hipSuccess) { tcct_set_error("pw_bwd_bn_sums_xaff: memset failed"); return -2; }
-    return pw_bwd_impl(y_prev, dz, w, res, dx, nullptr, dw, dbias, M, K, N, stream, false, TCCT_ACT_NONE, red_post,
-                       PwBnBwd{(const bf16*)y, nullptr, (const bf16*)y_prev, ab_prev, sums_prev, sums, raw, mean_rstd, ab, dgamma, dbeta}, false, TCCT_ACT_HSWISH);
-}
-static int pw_bwd_bn_impl(const void* x, const void* x2, const void* dz, PwBnBwd bn, int post, const float* w, const void* res, void* dx, void* dx2,
-                          float* dw, float* dbias, int64_t M, int K, int N, int red_post, tcct_stream_t stream) {
-    const void* y = bn.y; const void* y_prev = bn.yprev; const float* ab_prev = bn.abprev; double* sums_prev = bn.sums_prev;
-    const bool split = x2 != nullptr;
-    TCCT_CHECK(tcct_pw_bwd_bn_supported(K, N, post, red_post, split ? 1 : 0), "pw_bwd_bn: K=%d N=%d post=%d red_post=%d split=%d unsupported", K, N, post,
-               red_post, (int)split);
-    TCCT_CHECK(y != nullptr && (red_post < 0 || (y_prev && ab_prev && sums_prev)), "pw_bwd_bn: NULL argument");
-    TCCT_CHECK(!split || (dx2 != nullptr && res == nullptr), "pw_bwd_bn: the concatenated form takes x2 / dx2 and no residual");
-    if (red_post >= 0 && !tcct_skip_zero_fill() &&
-        hipMemsetAsync(sums_prev, 0, sizeof(double) * 2 * (split ? K / 2 : K), (hipStream_t)stream) != hipSuccess) { tcct_set_error("pw_bwd_bn: memset failed"); return -2; }
-    return pw_bwd_impl(x, dz, w, split ? x2 : res, dx, split ? dx2 : nullptr, dw, dbias, M, K, N, stream, split, post, red_post, bn);
+    TCCT_CHECK(y_prev && ab_prev && sums && mean_rstd && ab && dgamma && dbeta && (red_post < 0 || sums_prev), "pw_bwd_bn_sums_xaff: NULL argument");
+    PwBwdMode md;
+    md.bnp = TCCT_ACT_NONE; md.redp = red_post; md.xap = TCCT_ACT_HSWISH;
+    return pw_bwd_impl(y_prev, dz, w, res, dx, nullptr, dw, dbias, M, K, N, stream, md, pw_bn_sums(y, sums, raw, mean_rstd, ab, dgamma, dbeta, y_prev, ab_prev, sums_prev));
 }
 /* Backward of  y = gelu(x1) W^T + b  given dy, with x1 the PRE-activation (Mlp.fc1's output, reference nets/tcct.py:29-53): dx1 = (dy W) gelu'(x1),
  * dw += dy^T gelu(x1), dbias += sum dy in one pass; gelu(x1) is rebuilt while the tile is staged, the activation's own backward pass does not exist.
  * K = N in {64, 96}. */
 extern "C" int tcct_pw_bwd_gelu(const void* x1, const void* dy, const float* w, void* dx1, float* dw, float* dbias, int64_t M, int K, int N,
                                 tcct_stream_t stream) {
-    TCCT_CHECK(K == N && (K == 64 || K == 96), "pw_bwd_gelu: K=%d N=%d unsupported (64 or 96 square; 128 spills 30 VGPRs)", K, N);
-    return pw_bwd_impl(x1, dy, w, nullptr, dx1, nullptr, dw, dbias, M, K, N, stream, false, -1, -1,
-                       PwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr}, true);
+    PwBwdMode md;
+    md.gelu_x = true;
+    return pw_bwd_impl(x1, dy, w, nullptr, dx1, nullptr, dw, dbias, M, K, N, stream, md);
 }
 /* tcct_pw_bwd_residual2 with dy = dy_a + dy_b summed while the tile is staged (rounded to bf16 like the tensor a separate add pass wrote); K = N = 32 */
 extern "C" int tcct_pw_bwd_residual2_sum(const void* x, const void* dy_a, const void* dy_b, const float* w, const void* res, void* dx_sum, void* dx_plain, float* dw,
                                          float* dbias, int64_t M, int K, int N, tcct_stream_t stream) {
-    TCCT_CHECK(K == 32 && N == 32, "pw_bwd_residual2_sum: K=%d N=%d unsupported (32 x 32)", K, N);
     TCCT_CHECK(dy_b != nullptr && res != nullptr && dx_plain != nullptr && dx_plain != dx_sum, "pw_bwd_residual2_sum: needs dy_b, res and two distinct outputs");
-    return pw_bwd_impl(x, dy_a, w, res, dx_sum, dx_plain, dw, dbias, M, K, N, stream, false, -1, -1,
-                       PwBnBwd{(const bf16*)dy_b, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr}, false, -1, false, true);
+    PwBwdMode md;
+    md.dy2 = true;
+    return pw_bwd_impl(x, dy_a, w, res, dx_sum, dx_plain, dw, dbias, M, K, N, stream, md, pw_bn_dy2(dy_b));
 }
 /* Backward of  y = LN(t; gamma, beta) W^T + b  (MHCABlock.norm2 -> Mlp.fc1, reference nets/tcct.py:466-468) given dy, x = LN(t) as stored, t, the LayerNorm's
  * saved statistics mean_rstd [M][2] and res = the gradient reaching t through the residual path: dt = LN^T(dy W) + res, dw, dbias as tcct_pw_bwd, dgamma / dbeta
  * [K] of the LayerNorm (cleared here unless the outputs are pre-zeroed) -- one pass, the gradient of x is never written.  K = N = 64. */
 extern "C" int tcct_pw_bwd_lnb(const void* x, const void* dy, const float* w, const void* t, const float* mean_rstd, const float* gamma, const void* res,
                                void* dt, float* dw, float* dbias, float* dgamma, float* dbeta, int64_t M, int K, int N, tcct_stream_t stream) {
-    TCCT_CHECK(K == 64 && N == 64, "pw_bwd_lnb: K=%d N=%d unsupported (64 x 64)", K, N);
     TCCT_CHECK(t && mean_rstd && gamma && res && dgamma && dbeta, "pw_bwd_lnb: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (!tcct_skip_zero_fill() && (hipMemsetAsync(dgamma, 0, sizeof(float) * K, st) != hipSuccess || hipMemsetAsync(dbeta, 0, sizeof(float) * K, st) != hipSuccess)) {
-        tcct_set_error("pw_bwd_lnb: memset failed"); return -2;
-    }
-    return pw_bwd_impl(x, dy, w, res, dt, nullptr, dw, dbias, M, K, N, stream, false, -1, -1,
-                       PwBnBwd{nullptr, nullptr, (const bf16*)t, gamma, nullptr, nullptr, 0, mean_rstd, nullptr, dgamma, dbeta}, false, -1, true);
-}
-static int pw_bwd_impl(const void* x, const void* dy, const float* w, const void* res, void* dx, void* dx_plain, float* dw, float* dbias,
-                       int64_t M, int K, int N, tcct_stream_t stream, bool split, int bnp, int redp, PwBnBwd bn, bool gelu_x, int xap, bool lnb, bool dy2) {
-    TCCT_CHECK(K % 32 == 0 && N % 32 == 0 && K >= 32 && N >= 32 && K <= 128 && N <= 128, "pw_bwd: K=%d N=%d unsupported (32..128)", K, N);
-    TCCT_CHECK(M > 0 && M * (int64_t)(K > N ? K : N) * 2 < (1LL << 31), "pw_bwd: tensor exceeds the 2 GiB buffer-descriptor range");
-    hipStream_t st = (hipStream_t)stream;
-    if (!tcct_skip_zero_fill() && hipMemsetAsync(dw, 0, sizeof(float) * (size_t)N * K, st) != hipSuccess) { tcct_set_error("pw_bwd: memset failed"); return -2; }
-    if (dbias && !tcct_skip_zero_fill() && hipMemsetAsync(dbias, 0, sizeof(float) * N, st) != hipSuccess) { tcct_set_error("pw_bwd: memset failed"); return -2; }
-    const int NT = N / 32, KT = K / 32;
-    const int SX = 64 * KT + ((KT & 1) ? 0 : 64), SD = 64 * NT + ((NT & 1) ? 0 : 64), SW = 2 * N + 16;
-    const size_t lds = (size_t)PB_P * (SX + SD) + (((size_t)K * SW + 15) & ~(size_t)15) + 4 * 2560 + (bnp >= 0 ? (size_t)5 * N * 4 : 0) +
-                       ((redp >= 0 || xap >= 0 || lnb) ? (size_t)2 * K * 4 : 0);
-    TCCT_CHECK(lds <= 160 * 1024, "pw_bwd: %zu B of LDS", lds);
-    const int64_t tiles = (M + PB_P - 1) / PB_P;
-    int per_cu = (int)((160 * 1024) / (lds + 256));
-    if (per_cu > 2) per_cu = 2;
-    // (one block per CU looked better in tools/kbench.py -- 64->64 @L1 0.135 -> 0.125 ms, 32->32 @L0 0.258 -> 0.235 -- but inside the training
-    // step, where the tensors are not the same two buffers over and over, it was slower: k_pw_bwd 2.46 -> 2.57 ms per step; two per CU stay)
-    int64_t gx = 256 * per_cu;
-    if (gx > tiles) gx = tiles;
-#define BLX(NTV, KTV, SPV, BNV, RDV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_bwd<NTV, KTV, SPV, BNV, RDV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_bwd<NTV, KTV, SPV, BNV, RDV>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, w, (const bf16*)res, (bf16*)dx, (bf16*)dx_plain, dw, dbias, M, bn); }
-    if (dy2) {          // decoder block tail: the two output gradients summed on load (K = N = 32)
-        { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_bwd<1, 1, false, -1, -1, false, -1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; }
-          hipLaunchKernelGGL((k_pw_bwd<1, 1, false, -1, -1, false, -1, false, true>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, w, (const bf16*)res, (bf16*)dx, (bf16*)dx_plain, dw, dbias, M, bn); }
-        TCCT_LAUNCH_OK();
-    }
-    if (lnb) {          // fc1 behind MHCABlock.norm2: the LayerNorm backward in the dx epilogue (K = N = 64)
-#define BLN(T) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_bwd<T, T, false, -1, -1, false, -1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_bwd<T, T, false, -1, -1, false, -1, true>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, w, (const bf16*)res, (bf16*)dx, (bf16*)dx_plain, dw, dbias, M, bn); }
-        BLN(2)
-#undef BLN
-        TCCT_LAUNCH_OK();
-    }
-    if (xap >= 0) {     // x = hswish(a y_prev + b) applied on load (InvRes.norm -> conv2): BN behind without activation; 64: + the reduction epilogue
-#define BLXA(NTV, RDV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_bwd<NTV, NTV, false, 0, RDV, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_bwd<NTV, NTV, false, 0, RDV, false, 2>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, w, (const bf16*)res, (bf16*)dx, (bf16*)dx_plain, dw, dbias, M, bn); }
-        if (NT == 2 && redp == TCCT_ACT_HSWISH) BLXA(2, 2) else if (NT == 3 && redp < 0) BLXA(3, -1)
-        else { tcct_set_error("pw_bwd: x-affine form K=N=%d red_post=%d has no kernel", K, redp); return -1; }
-#undef BLXA
-        TCCT_LAUNCH_OK();
-    }
-    if (bnp >= 0) {
-        // the combinations the network has (tcct_pw_bwd_bn_supported): every extra instantiation of this kernel costs ~a minute of hipcc
-        const int H = TCCT_ACT_HSWISH;
-#define BN_SQ(T) \
-        if (bnp == 0 && redp < 0) BLX(T, T, false, 0, -1) else BLX(T, T, false, 2, -1)
-#define BN_SQR(T) \
-        if (bnp == 0 && redp == 0) BLX(T, T, false, 0, 0) else if (bnp == 0 && redp == H) BLX(T, T, false, 0, 2) \
-        else if (bnp == H && redp == 0) BLX(T, T, false, 2, 0) else BLX(T, T, false, 2, 2)
-        static_assert(TCCT_ACT_HSWISH == 2 && TCCT_ACT_NONE == 0, "activation codes are template arguments below");
-        if (split) BLX(3, 4, true, 2, -1)
-        else if (NT == 1 && KT == 1) BLX(1, 1, false, 0, -1)
-        else if (NT == 1 && KT == 3) BLX(1, 3, false, 0, -1)
-        else if (NT == 1 && KT == 4) BLX(1, 4, false, 0, -1)
-        else if (NT == 2) { if (redp < 0) { BN_SQ(2) } else { BN_SQR(2) } }
-        else { BN_SQ(3) }
-#undef BN_SQ
-#undef BN_SQR
-        TCCT_LAUNCH_OK();
-    }
-    if (gelu_x) {
-#define BLG(T) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_bwd<T, T, false, -1, -1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_bwd<T, T, false, -1, -1, true>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, w, (const bf16*)res, (bf16*)dx, (bf16*)dx_plain, dw, dbias, M, bn); }
-        if (NT == 2) BLG(2) else BLG(3)
-#undef BLG
-        TCCT_LAUNCH_OK();
-    }
-    if (split && KT == 2) { BLX(1, 2, true, -1, -1) TCCT_LAUNCH_OK(); }     // two halves of 32 channels (checked by the caller: N = 32)
-#define BL(NTV, KTV) BLX(NTV, KTV, false, -1, -1)
-#define BLS(NTV) BLX(NTV, 4, true, -1, -1)
-#define BLK(NTV) switch (KT) { case 1: BL(NTV, 1) break; case 2: BL(NTV, 2) break; case 3: BL(NTV, 3) break; default: if (split) BLS(NTV) else BL(NTV, 4) break; }
-    switch (NT) { case 1: BLK(1) break; case 2: BLK(2) break; case 3: BLK(3) break; default: BLK(4) break; }
-#undef BLK
-#undef BLS
-#undef BL
-#undef BLX
-    TCCT_LAUNCH_OK();
+    PwBwdMode md;
+    md.lnb = true;
+    return pw_bwd_impl(x, dy, w, res, dt, nullptr, dw, dbias, M, K, N, stream, md, pw_bn_ln_front(t, gamma, mean_rstd, dgamma, dbeta));
 }
 
 // ------------------------------------------------------------------------------------------------ forward, tile-staged
@@ -1715,9 +1720,50 @@ static bool pw_fwd2_ok(int64_t M, int K, int N, int K1, bool has_x2) {
     if (has_x2 && !(K == 128 && K1 == 64)) return false;
     return true;
 }
+// THE list of k_pw_fwd2 kernels: a row is the template arguments and the launcher of exactly that instantiation; a combination without a row is an error
+// (pw_fwd2_launch), never a neighbouring kernel, and pw_fwd2_aff_ok answers from here.  A form is added by adding its row.
+typedef void (*PwFwd2Launch)(dim3, dim3, size_t, hipStream_t, const bf16*, const bf16*, const float*, const float*, bf16*, int64_t, double*, int, PwRes);
+struct PwFwd2Row { int nt, kt; bool stats, split, res, gx; int xap; bool aff; PwFwd2Launch launch; };
+#define PF2_ROW(NT, KT, ST, SP, RS, GX, XA, AF) {NT, KT, ST, SP, RS, GX, XA, AF, tcct_launch<k_pw_fwd2<NT, KT, ST, SP, RS, GX, XA, AF>, 160 * 1024>}
+#define PF2_TRAIN(NT, KT, ST, SP, RS) PF2_ROW(NT, KT, ST, SP, RS, false, -1, false)
+#define PF2_KT(NT, ST, RS) PF2_TRAIN(NT, 2, ST, false, RS), PF2_TRAIN(NT, 3, ST, false, RS), PF2_TRAIN(NT, 4, ST, false, RS)
+#define PF2_SQ(T, ST, RS, GX, XA, AF) PF2_ROW(T, T, ST, false, RS, GX, XA, AF)
+static const PwFwd2Row pw_fwd2_table[] = {
+    // training: K in 64 .. 128, N in 32 .. 128; plain, with the BatchNorm statistics of the consumer, with the residual epilogue
+    PF2_KT(1, false, false), PF2_KT(2, false, false), PF2_KT(3, false, false), PF2_KT(4, false, false),
+    PF2_KT(1, true, false), PF2_KT(2, true, false), PF2_KT(3, true, false), PF2_KT(4, true, false),
+    PF2_KT(1, false, true), PF2_KT(2, false, true), PF2_KT(3, false, true), PF2_KT(4, false, true),
+    // ... over the concatenation of two 64-channel tensors, without / with statistics
+    PF2_TRAIN(1, 4, false, true, false), PF2_TRAIN(2, 4, false, true, false), PF2_TRAIN(3, 4, false, true, false), PF2_TRAIN(4, 4, false, true, false),
+    PF2_TRAIN(1, 4, true, true, false), PF2_TRAIN(2, 4, true, true, false), PF2_TRAIN(3, 4, true, true, false), PF2_TRAIN(4, 4, true, true, false),
+    // x = hswish(BatchNorm(y_prev)) applied on load + statistics (InvRes.norm -> conv2); x = gelu(x1) applied on load + residual (Mlp.fc1 -> fc2)
+    PF2_SQ(2, true, false, false, 2, false), PF2_SQ(3, true, false, false, 2, false),
+    PF2_SQ(2, false, true, true, -1, false), PF2_SQ(3, false, true, true, -1, false),
+    // inference epilogue (eval-mode BatchNorm + activation): square without / with the residual, the concatenated 64 + 64 -> 96, with BatchNorm + Hardswish on load
+    PF2_SQ(2, false, false, false, -1, true), PF2_SQ(3, false, false, false, -1, true), PF2_SQ(4, false, false, false, -1, true),
+    PF2_SQ(2, false, true, false, -1, true), PF2_SQ(3, false, true, false, -1, true), PF2_SQ(4, false, true, false, -1, true),
+    PF2_ROW(3, 4, false, true, false, false, -1, true),
+    PF2_SQ(2, false, true, false, 2, true), PF2_SQ(3, false, true, false, 2, true), PF2_SQ(4, false, true, false, 2, true),
+};
+#undef PF2_SQ
+#undef PF2_KT
+#undef PF2_TRAIN
+#undef PF2_ROW
+static const PwFwd2Row* pw_fwd2_find(int K, int N, bool stats, bool split, bool res, bool gx, int xap, bool aff) {
+    if (K % 32 || N % 32) return nullptr;
+    for (const PwFwd2Row& r : pw_fwd2_table)
+        if (r.nt == N / 32 && r.kt == K / 32 && r.stats == stats && r.split == split && r.res == res && r.gx == gx && r.xap == xap && r.aff == aff) return &r;
+    return nullptr;
+}
+static bool pw_fwd2_aff_ok(int64_t M, int K, int N, bool has_x2, bool has_res) {
+    if (M * (int64_t)(K > N ? K : N) * 2 >= (1LL << 31)) return false;
+    return pw_fwd2_find(K, N, false, has_x2, has_res, false, -1, true) != nullptr;
+}
 static int pw_fwd2_launch(const void* x, const void* x2, const float* w, const float* bias, void* y, int64_t M, int K, int N, double* stats,
-                          int stat_pre, tcct_stream_t stream, PwRes pr, bool gelu_x) {
-    const int NT = N / 32, KT = K / 32;
+                          int stat_pre, tcct_stream_t stream, PwRes pr, const PwFwd2Mode& md) {
+    const PwFwd2Row* row = pw_fwd2_find(K, N, stats != nullptr, x2 != nullptr, pr.res != nullptr, md.gelu_x, md.xap, pr.has_aff != 0);
+    TCCT_CHECK(row != nullptr && (md.xap >= 0) == (pr.xab != nullptr), "pw_fwd2: K=%d N=%d unsupported: no kernel for NT=%d KT=%d STATS=%d SPLIT=%d RES=%d GX=%d XAP=%d AFF=%d", K, N,
+               N / 32, K / 32, stats != nullptr, x2 != nullptr, pr.res != nullptr, (int)md.gelu_x, md.xap, pr.has_aff);
     const size_t lds = (size_t)PB_P * (2 * K + 16) + (size_t)N * (2 * K + 16) + (size_t)N * 4 + 4 * 2560 + (pr.xab ? (size_t)2 * K * 4 : 0) + (pr.has_aff ? (size_t)2 * N * 4 : 0);
     const int64_t tiles = (M + PB_P - 1) / PB_P;
     int per_cu = (int)((160 * 1024) / (lds + 256));
@@ -1725,70 +1771,29 @@ static int pw_fwd2_launch(const void* x, const void* x2, const float* w, const f
     // (as for k_pw_bwd: one block per CU won by 3-10 % in the micro-benchmark and lost inside the step -- the statistics variants by 60 %)
     int64_t gx = 256 * per_cu;
     if (gx > tiles) gx = tiles;
-    hipStream_t st = (hipStream_t)stream;
-#define F2(NTV, KTV, SV, PV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd2<NTV, KTV, SV, PV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd2<NTV, KTV, SV, PV>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr); }
-#define F2R(NTV, KTV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd2<NTV, KTV, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd2<NTV, KTV, false, false, true>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr); }
-#define F2K(NTV, SV) switch (KT) { case 2: F2(NTV, 2, SV, false) break; case 3: F2(NTV, 3, SV, false) break; default: if (x2) F2(NTV, 4, SV, true) else F2(NTV, 4, SV, false) break; }
-#define F2RK(NTV) switch (KT) { case 2: F2R(NTV, 2) break; case 3: F2R(NTV, 3) break; default: F2R(NTV, 4) break; }
-#define F2N(SV) switch (NT) { case 1: F2K(1, SV) break; case 2: F2K(2, SV) break; case 3: F2K(3, SV) break; default: F2K(4, SV) break; }
-#define F2G(T) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd2<T, T, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd2<T, T, false, false, true, true>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr); }
-#define F2A(T) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd2<T, T, true, false, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd2<T, T, true, false, false, false, 2>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr); }
-#define F2F(NTV, KTV, SPV, RSV) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd2<NTV, KTV, false, SPV, RSV, false, -1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd2<NTV, KTV, false, SPV, RSV, false, -1, true>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr); }
-#define F2X(T) { static bool at_ = false; if (!at_) { (void)hipFuncSetAttribute((const void*)k_pw_fwd2<T, T, false, false, true, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); at_ = true; } \
-        hipLaunchKernelGGL((k_pw_fwd2<T, T, false, false, true, false, 2, true>), dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr); }
-    if (pr.has_aff && pr.xab) {           // inference: BatchNorm + Hardswish in front applied on load, BatchNorm behind + residual in the epilogue (square 64 / 96 / 128)
-        if (NT == 2) F2X(2) else if (NT == 3) F2X(3) else F2X(4)
-    }
-    else
-    if (pr.has_aff) {           // inference epilogues (pw_fwd2_aff_ok lists the shapes)
-        if (x2) F2F(3, 4, true, false)
-        else if (pr.res) { if (NT == 2) F2F(2, 2, false, true) else if (NT == 3) F2F(3, 3, false, true) else F2F(4, 4, false, true) }
-        else { if (NT == 2) F2F(2, 2, false, false) else if (NT == 3) F2F(3, 3, false, false) else F2F(4, 4, false, false) }
-    }
-    else
-    if (pr.xab) { if (NT == 2) F2A(2) else F2A(3) }
-    else
-    if (gelu_x) { if (NT == 2) F2G(2) else F2G(3) }
-    else
-    if (pr.res) { switch (NT) { case 1: F2RK(1) break; case 2: F2RK(2) break; case 3: F2RK(3) break; default: F2RK(4) break; } }
-    else if (stats) { F2N(true) } else { F2N(false) }
-#undef F2X
-#undef F2F
-#undef F2G
-#undef F2A
-#undef F2RK
-#undef F2R
-#undef F2N
-#undef F2K
-#undef F2
+    row->launch(dim3((unsigned)gx), dim3(PWB), lds, (hipStream_t)stream, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr);
     TCCT_LAUNCH_OK();
 }
 
-static int pw_fwd2_route(const void* x, const void* x2, const float* w, const float* bias, void* y, int64_t M, int K, int N, double* stats,
-                         int stat_pre, tcct_stream_t stream, const bf16* res, const float* rscale, int64_t per_sample, bf16* yplain) {
-    return pw_fwd2_launch(x, x2, w, bias, y, M, K, N, stats, stat_pre, stream, PwRes{res, rscale, per_sample, yplain});
-}
 /* y = hswish(a_prev y_prev + b_prev) W^T + bias with the statistics of y for the BatchNorm behind (stats fp64 [2N], zero on entry): the convolution
  * whose input is a train-mode BatchNorm + Hardswish it alone consumes (InvRes.norm -> conv2, nets/tcct.py:563-572), the normalisation applied while the
  * tile is staged; ab_prev = {a[K], b[K]}.  K = N in {64, 96}. */
 extern "C" int tcct_pw_fwd_bnstats_xaff(const void* y_prev, const float* ab_prev, const float* w, const float* bias, void* y, int64_t M, int K, int N,
                                         double* stats, tcct_stream_t stream) {
-    TCCT_CHECK(K == N && (K == 64 || K == 96) && ab_prev && stats, "pw_fwd_bnstats_xaff: K=%d N=%d unsupported (64 or 96 square) or NULL argument", K, N);
-    TCCT_CHECK(M > 0 && M * (int64_t)K * 2 < (1LL << 31), "pw_fwd_bnstats_xaff: tensor exceeds the 2 GiB buffer-descriptor range");
-    return pw_fwd2_launch(y_prev, nullptr, w, bias, y, M, K, N, stats, 0, stream, PwRes{nullptr, nullptr, 1, nullptr, ab_prev});
+    TCCT_CHECK(ab_prev && stats, "pw_fwd_bnstats_xaff: NULL argument");
+    TCCT_CHECK(M > 0 && M * (int64_t)(K > N ? K : N) * 2 < (1LL << 31), "pw_fwd_bnstats_xaff: tensor exceeds the 2 GiB buffer-descriptor range");
+    PwFwd2Mode md;
+    md.xap = TCCT_ACT_HSWISH;
+    return pw_fwd2_launch(y_prev, nullptr, w, bias, y, M, K, N, stats, 0, stream, pw_res_xaff(ab_prev), md);
 }
 /* y = res + scale[m / per_sample] * (gelu(x1) W^T + bias) with x1 the PRE-activation of Mlp.fc1 (reference nets/tcct.py:29-53,468): Mlp.fc2 with the
  * activation applied while the tile is staged and the DropPath scale + residual add in the epilogue; scale nullable.  K = N in {64, 96}. */
 extern "C" int tcct_pw_fwd_gelu_residual(const void* x1, const float* w, const float* bias, const void* res, const float* scale, int64_t per_sample,
                                          void* y, int64_t M, int K, int N, tcct_stream_t stream) {
-    TCCT_CHECK(K == N && (K == 64 || K == 96), "pw_fwd_gelu_residual: K=%d N=%d unsupported (64 or 96 square, as tcct_pw_bwd_gelu)", K, N);
-    TCCT_CHECK(res != nullptr && per_sample >= 1 && M > 0 && M * (int64_t)K * 2 < (1LL << 31), "pw_fwd_gelu_residual: needs res, per_sample >= 1, < 2 GiB tensors");
-    return pw_fwd2_launch(x1, nullptr, w, bias, y, M, K, N, nullptr, 0, stream, PwRes{(const bf16*)res, scale, per_sample, nullptr}, true);
+    TCCT_CHECK(res != nullptr && per_sample >= 1 && M > 0 && M * (int64_t)(K > N ? K : N) * 2 < (1LL << 31), "pw_fwd_gelu_residual: needs res, per_sample >= 1, < 2 GiB tensors");
+    PwFwd2Mode md;
+    md.gelu_x = true;
+    return pw_fwd2_launch(x1, nullptr, w, bias, y, M, K, N, nullptr, 0, stream, pw_res_train((const bf16*)res, scale, per_sample, nullptr), md);
 }
 
 // ------------------------------------------------------------------------------------------------ first-layer im2col

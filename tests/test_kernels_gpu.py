@@ -2591,3 +2591,53 @@ def test_wide_convolution_output_slabs_with_eval_batchnorm_epilogue():
     conv = F.conv2d(x, w.bfloat16().float(), None, 1, 1)
     want = F.hardswish((conv - rm.view(1, -1, 1, 1)) / torch.sqrt(rv.view(1, -1, 1, 1) + 1e-5) * gamma.view(1, -1, 1, 1) + beta.view(1, -1, 1, 1))
     torch.testing.assert_close(nchw(y), want, rtol=2e-2, atol=2e-2 * max(1.0, want.abs().max().item()))
+
+
+def test_pw_bwd_bn_supported_is_the_documented_list():
+    """tcct_pw_bwd_bn_supported (answered from the k_pw_bwd kernel table) over every (K, N) in {32..160}^2, post / red_post in {-1..5}, split in {0, 1} against the contract
+    written above the function: K = N in {64, 96} (the reduction epilogue only at 64); N = 32 with K in {32, 96, 128}, post none, no reduction; the concatenated 128 -> 96
+    with Hardswish, no reduction; post / red_post in {none, Hardswish} (red_post -1: no reduction epilogue)"""
+    import itertools
+    from tcct_amd._lib import lib
+    NONE, HSWISH = 0, 2
+    for K, N, post, red, split in itertools.product((32, 64, 96, 128, 160), (32, 64, 96, 128, 160), range(-1, 6), range(-1, 6), (0, 1)):
+        if post not in (NONE, HSWISH) or red not in (-1, NONE, HSWISH):
+            want = False
+        elif split:
+            want = (K, N, post, red) == (128, 96, HSWISH, -1)
+        elif K == N and K in (64, 96):
+            want = red == -1 or K == 64
+        elif N == 32 and K in (32, 96, 128):
+            want = post == NONE and red == -1
+        else:
+            want = False
+        assert bool(lib.pw_bwd_bn_supported(K, N, post, red, split)) == want, (K, N, post, red, split)
+
+
+@pytest.mark.parametrize('entry', ['pw_fwd_bnstats_xaff', 'pw_fwd_gelu_residual', 'pw_bwd_gelu', 'pw_bwd_lnb', 'pw_bwd_bn_sums_xaff'])
+def test_pointwise_form_without_a_kernel_is_refused(entry):
+    """the fused pointwise forms exist at 64 / 96 channels (the LayerNorm form at 64): at K = N = 128 the kernel tables have no row, and the entry must say so (TcctError)
+    before anything is cleared or launched -- not run the neighbouring 96-channel kernel.  Every output keeps its fill value."""
+    from tcct_amd._lib import lib, TcctError
+    M, C = 256, 128
+    bf = lambda seed: rnd(M, C, seed=seed, dt=torch.bfloat16).cuda().bfloat16()
+    f32 = lambda *shape: torch.full(shape, 7.0, device='cuda')
+    x, dy, y, res = bf(1), bf(2), bf(3), bf(4)
+    w, bias, ab = rnd(C, C, seed=5).cuda() / C ** 0.5, rnd(C, seed=6).cuda(), torch.cat([1 + 0.1 * rnd(C, seed=7), 0.1 * rnd(C, seed=8)]).cuda()
+    out, dw, db, dg, dbeta = torch.full((M, C), 7.0, device='cuda', dtype=torch.bfloat16), f32(C, C), f32(C), f32(C), f32(C)
+    sums, sums_prev = torch.full((2 * C,), 7.0, device='cuda', dtype=torch.float64), torch.full((2 * C,), 7.0, device='cuda', dtype=torch.float64)
+    mean_rstd_c, mean_rstd_m = torch.cat([torch.zeros(C), torch.ones(C)]).cuda(), torch.stack([torch.zeros(M), torch.ones(M)], 1).contiguous().cuda()
+    with pytest.raises(TcctError):
+        if entry == 'pw_fwd_bnstats_xaff':
+            lib.pw_fwd_bnstats_xaff(x, ab, w, bias, out, M, C, C, sums)
+        elif entry == 'pw_fwd_gelu_residual':
+            lib.pw_fwd_gelu_residual(x, w, bias, res, None, M, out, M, C, C)
+        elif entry == 'pw_bwd_gelu':
+            lib.pw_bwd_gelu(x, dy, w, out, dw, db, M, C, C)
+        elif entry == 'pw_bwd_lnb':
+            lib.pw_bwd_lnb(x, dy, w, y, mean_rstd_m, ab, res, out, dw, db, dg, dbeta, M, C, C)
+        else:
+            lib.pw_bwd_bn_sums_xaff(x, ab, dy, y, sums, 0, mean_rstd_c, ab, dg, dbeta, w, res, out, dw, db, M, C, C, -1, sums_prev)
+    torch.cuda.synchronize()
+    for t in (out, dw, db, dg, dbeta, sums, sums_prev):
+        assert bool((t == 7).all())

@@ -3,7 +3,7 @@
 verdict: a run-time `switch` over activation kinds keeps every branch in the loop body although one runs, so read the loop before acting (and tools/step_valu.sh tells which
 kernels spend their cycles issuing VALU instructions at all).
 
-    python tools/isa_scan.py [file.hip ...]      (default: every tcct_amd/csrc/*.hip; compiles with --save-temps into a temporary directory, ~1-2 min per file)"""
+    python tools/isa_scan.py [file.hip ...]      (default: every tcct_amd/csrc/*.hip; compiles the device side to assembly in a temporary directory, ~1-2 min per file)"""
 import collections
 import glob
 import os
@@ -16,6 +16,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'tcct_amd', 'csrc')
 SLOW = ('v_div_scale_f32', 'v_div_fmas_f32', 'v_div_fixup_f32', 'v_sqrt_f32', 'v_div_scale_f64', 'v_rcp_f64', 'v_rsq_f64', 'v_sqrt_f64', 'v_fma_f64', 'v_mul_f64', 'v_add_f64',
         'v_cvt_f64_f32', 'v_mul_lo_u32', 'v_mul_hi_u32', 'v_mad_u64_u32', 'v_log_f32', 'scratch_')
+
+
+def compile_asm(src, outdir):
+    """Device code of one .hip source as gfx950 assembly (the library's flags, device side only): returns (path of the .s or None, compiler output).  Shared with isa_equal.py."""
+    asm = os.path.join(outdir, os.path.splitext(os.path.basename(src))[0] + '.s')
+    r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '--cuda-device-only', '-S', os.path.abspath(src), '-o', asm],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    return (asm if r.returncode == 0 and os.path.exists(asm) else None), r.stdout
 
 
 def scan(asm):
@@ -50,11 +58,9 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         for f in files:
             base = os.path.splitext(os.path.basename(f))[0]
-            r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-c', os.path.abspath(f), '-o', base + '.o', '--save-temps'],
-                               cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            asm = os.path.join(tmp, base + '-hip-amdgcn-amd-amdhsa-gfx950.s')
-            if r.returncode != 0 or not os.path.exists(asm):
-                print(f'# {base}: compile failed\n' + r.stdout[-800:])
+            asm, log = compile_asm(f, tmp)
+            if asm is None:
+                print(f'# {base}: compile failed\n' + log[-800:])
                 continue
             rows += [(n, base, name, nl, d) for n, name, nl, d in scan(asm)]
     rows.sort(reverse=True)
