@@ -638,6 +638,25 @@ int tcct_dwk_strided_fwd(const void* x, int64_t ldx, const float* w, const float
 int tcct_dwk_strided_wgrad(const void* x, int64_t ldx, const void* dy, int64_t ldy, float* dw, float* dbias, int B, int H, int W, int Cg,
                            int K, int dtype, tcct_stream_t stream);
 
+/* ---- Hydra attention, reference nets/tcct.py:343-403 (HydraAttention; commented out in MHCABlock, tcct.py:435-441) ------
+ * Same qkv layout and crpe term as the tcct_fatt_* family above (channel = which*C + head*Ch + ch; cv from tcct_dwk_strided_fwd), with Ch = C/heads a
+ * multiple of 4, Ch <= 32, C <= 256.  kv, dkv fp32 [B,C].  One lane per (token, head): the per-head norms are lane-local; inverse norms by v_rsq_f32,
+ * no epsilon (tcct.py:374-375).  The reductions over the tokens go through per-block partials in `workspace` and one ordered combine: no atomics, the
+ * results are bit-identical from run to run. */
+int64_t tcct_hydra_kv_workspace_bytes(int B, int64_t N, int C);
+/* kv = sum_n (k / |k|) * v   (tcct.py:375-376: `k = k / k.norm(dim=-1, keepdim=True)`, `(k * v).sum(dim=-2, keepdim=True)`) */
+int tcct_hydra_kv(const void* qkv, void* workspace, float* kv, int B, int64_t N, int C, int heads, int dtype, tcct_stream_t stream);
+/* dkv = scale * sum_n dmix * (q / |q|)   (gradient of kv through `out = q * kv`, tcct.py:377, and `self.scale * factor_att`, tcct.py:396) */
+int tcct_hydra_dkv(const void* qkv, const void* dmix, void* workspace, float* dkv, float scale, int B, int64_t N, int C, int heads, int dtype,
+                   tcct_stream_t stream);
+/* mix [B,N,C] = scale * (q / |q|) * kv + q * cv   (tcct.py:374, 377, 393-397, 285; already in the transpose(1,2).reshape(B,N,C) layout) */
+int tcct_hydra_apply_fwd(const void* qkv, const float* kv, const void* cv, void* mix, float scale, int B, int64_t N, int C, int heads,
+                         int dtype, tcct_stream_t stream);
+/* dqkv [B,N,3C] = ((g - qn (qn.g)) / |q| + dmix cv | (e - kn (kn.e)) / |k| | dkv kn) with g = scale dmix kv, e = dkv v; dcv [B,N,C] = dmix * q
+ * (backward of tcct.py:374-377, 396); the crpe convolution's share of dv is added by tcct_dwk_strided_fwd(flip=1, accumulate=1) on dcv afterwards */
+int tcct_hydra_apply_bwd(const void* qkv, const float* kv, const float* dkv, const void* cv, const void* dmix, void* dqkv, void* dcv,
+                         float scale, int B, int64_t N, int C, int heads, int dtype, tcct_stream_t stream);
+
 /* ---- clip_grad_norm_(12) + AdamW on flat fp32 buffers (kite/loop_seg.py:128-130, kite/loopback.py:127) ------ */
 int tcct_grad_sumsq(const float* g, int64_t n, double* acc, tcct_stream_t stream);
 /* grad_mul pre-scales the raw gradient (1/world_size after a sum all-reduce); total_norm_out nullable */

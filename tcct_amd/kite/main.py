@@ -45,9 +45,9 @@ def build_parser():
     p.add_argument('--pl', type=str2bool, default=False, help='Parallel: one process per GPU (torchrun)')
     p.add_argument('--bug', type=str2bool, default=False, help='Debug Mode!')
     p.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'fp32'], help='compute dtype of activations')
-    p.add_argument('--att', type=str, default='pool', choices=['pool', 'factor'],
-                   help="token mixer of the ViT blocks: 'pool' = MetaPool (reference nets/tcct.py:449); 'factor' = the factorised attention the "
-                        "reference keeps commented out (nets/tcct.py:443-448; --net=stc_tt / tcct only)")
+    p.add_argument('--att', type=str, default='pool', choices=['pool', 'factor', 'hydra'],
+                   help="token mixer of the ViT blocks: 'pool' = MetaPool (reference nets/tcct.py:449); 'factor' / 'hydra' = the factorised attention / "
+                        "HydraAttention the reference keeps commented out (nets/tcct.py:435-448; --net=stc_tt / tcct only)")
     p.add_argument('--graph', type=str2bool, default=False,
                    help='EXPERIMENTAL: replay the training step from a hipGraph (launch-bound crop sizes such as the 256x256 of the reference '
                         'recipe; single process, fixed batch shape).  A capture late in a long process has crashed inside hipGraphLaunch '

@@ -255,8 +255,8 @@ class ConvPosEnc(nn.Module):
 
 class ConvRelPosEnc(nn.Module):
     """reference nets/tcct.py:219-287.  With the default pooling mixer these are parameters only (never executed by stc_tt; kept for
-    checkpoint parity); with `att='factor'` FactorAtt_ConvRelPosEnc runs them through `ops.factor_att` (depthwise 3/5/7 windows over
-    the head splits of v, times q)."""
+    checkpoint parity); with `att='factor'` / `att='hydra'` FactorAtt_ConvRelPosEnc / HydraAttention run them through `ops.factor_att` /
+    `ops.hydra_att` (depthwise 3/5/7 windows over the head splits of v, times q)."""
 
     def __init__(self, Ch, h, window):
         super().__init__()
@@ -297,6 +297,31 @@ class FactorAtt_ConvRelPosEnc(nn.Module):
         return ops.conv2d(self.mix(x, size), self.proj.weight, self.proj.bias)
 
 
+class HydraAttention(nn.Module):
+    """reference nets/tcct.py:343-403: the other token mixer the reference keeps commented out in MHCABlock (tcct.py:435-441).  Same parameters
+    as FactorAtt_ConvRelPosEnc (qkv / proj pointwise GEMMs, the shared crpe); between them q and k are normalised per head and token, k * v is summed
+    over the tokens per channel and multiplied onto q (`tcct_hydra_*` kernels), plus the same convolutional relative position term (`tcct_dwk_*`).
+    The crpe head splits (2+3+3) need num_heads = 8; attn_drop / proj_drop are 0 in the reference (DROP_RATE, tcct.py:26)."""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, shared_crpe=None):
+        super().__init__()
+        self.num_heads = num_heads
+        self.scale = qk_scale or (dim // num_heads) ** -0.5
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.proj = nn.Linear(dim, dim)
+        self.crpe = shared_crpe
+
+    def mix(self, x, size):
+        """everything up to (not including) the output projection: tokens [B,N,C] -> [B,N,C]"""
+        if sum(self.crpe.channel_splits) != x.shape[-1]:
+            raise ValueError(f'crpe head splits {self.crpe.head_splits} do not cover {self.num_heads} heads')
+        qkv = ops.conv2d(x, self.qkv.weight, self.qkv.bias)
+        return ops.hydra_att(qkv, size, self.num_heads, self.scale, self.crpe.conv_list)
+
+    def forward(self, x, size):
+        return ops.conv2d(self.mix(x, size), self.proj.weight, self.proj.bias)
+
+
 class Mlp(nn.Module):
     """reference nets/tcct.py:29-53"""
 
@@ -315,8 +340,10 @@ class MHCABlock(nn.Module):
         self.crpe = shared_crpe
         if att == 'factor':     # the commented-out alternative of the reference (tcct.py:443-448), qkv_bias=True (MHCABlock default :424)
             self.att = FactorAtt_ConvRelPosEnc(dim, num_heads=num_heads, qkv_bias=True, shared_crpe=shared_crpe)
+        elif att == 'hydra':    # the other commented-out alternative (tcct.py:435-441), same constructor arguments
+            self.att = HydraAttention(dim, num_heads=num_heads, qkv_bias=True, shared_crpe=shared_crpe)
         elif att != 'pool':
-            raise ValueError(f"att must be 'pool' (MetaPool, tcct.py:449) or 'factor', got {att!r}")
+            raise ValueError(f"att must be 'pool' (MetaPool, tcct.py:449), 'factor' or 'hydra', got {att!r}")
         self.mlp = Mlp(dim, dim * mlp_ratio)
         self.drop_prob = float(drop_path)
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
@@ -497,7 +524,7 @@ class MPViT(nn.Module):
     def __init__(self, embed_dims=(64, 96, 128, 160), mlp_ratios=(1, 1, 1, 1), num_heads=(4, 4, 4, 4),
                  drop_path_rate=0.1, num_classes=1000, att='pool'):
         super().__init__()
-        if att == 'factor':     # the crpe windows {3:2, 5:3, 7:3} split 8 heads (tcct.py:484-488); mpvit_tiny's 4 only fit the pooling mixer
+        if att in ('factor', 'hydra'):     # the crpe windows {3:2, 5:3, 7:3} split 8 heads (tcct.py:484-488); mpvit_tiny's 4 only fit the pooling mixer
             num_heads = (8, 8, 8, 8)
         self.att = att
         self.num_stages = 4

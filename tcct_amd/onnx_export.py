@@ -206,7 +206,7 @@ class _Emit:
         r = self.cba(p_st + '.InvRes.conv2.conv', p_st + '.InvRes.conv2.bn', r, res=pch)
         blk = p_st + '.mhca_blks.0.MHCA_layers.0'
         if (blk + '.att.qkv.weight') in self.sd:
-            raise TcctError("onnx export: the factorised-attention variant (att='factor') is not exported")
+            raise TcctError("onnx export: the attention variants (att='factor', att='hydra') are not exported")
         img = self.g.op('Add', [pch, self.conv(p_st + '.mhca_blks.0.cpe.proj', pch, pad=(1, 1), groups=C)], 'cpe')
         shape = self.g.op('Shape', [img], 'shape')
         t = self.g.op('Transpose', [self.g.op('Reshape', [img, self.g.const(np.array([0, C, -1], dtype=np.int64))])], 'tok', perm=[0, 2, 1])
