@@ -26,6 +26,8 @@ typedef void* tcct_stream_t;
 enum { TCCT_F32 = 0, TCCT_BF16 = 1 };
 enum { TCCT_ACT_NONE = 0, TCCT_ACT_LRELU = 1, TCCT_ACT_HSWISH = 2, TCCT_ACT_GELU = 3, TCCT_ACT_SIGMOID = 4,
        TCCT_ACT_ABS = 5 };
+/* per-class loss of MultiLoss (tcct_softmax_crit_*, tcct_upcrit_*, tcct_crit_ds_fwd) */
+enum { TCCT_CRIT_DICE = 0, TCCT_CRIT_DICE2 = 1, TCCT_CRIT_IOU = 2, TCCT_CRIT_MSE = 3 };
 
 int tcct_version(void);
 const char* tcct_last_error(void);
@@ -544,6 +546,22 @@ int tcct_updice_bwd(const float* low, const uint8_t* labels, int B, int h, int w
  * (head i at i*3C: pass the slices to tcct_softmax_dice_bwd / tcct_updice_bwd with grad_scale = coff). */
 int tcct_dice_ds_fwd(const void* logits, int dtype, const uint8_t* labels, int B, int H, int W, int C, const float* low1, int h1, int w1, const float* low2,
                      int h2, int w2, const float* low3, int h3, int w3, float coff, double* sums, float* loss, tcct_stream_t stream);
+/* ---- MultiLoss(<per-class loss>, weight=...) (kite/losses/loss.py:9-99): the five entry points above with a criterion `kind` (TCCT_CRIT_*) and per-class weights.
+ * p = softmax(logits) over C, g = one-hot(label), sums over all M = B*H*W pixels per class, loss = sum_c class_w[c] * L_c with
+ *   dice  1 - (1 + 2 sum pg) / (1 + sum p + sum g)        dice2 (DiceLoss(bi=True))  1 - (1 + 2 sum pg) / (1 + sum p^2 + sum g)
+ *   iou   1 - (sum pg + 1e-12) / (sum p + sum g - sum pg + 1e-12)        mse (nn.MSELoss, float one-hot target)  sum (p - g)^2 / M
+ * class_w: device fp32 [C], NULL = all ones.  sums fp64 [3][C] = {sum pg (mse: sum (p-g)^2), sum p (dice2: sum p^2; mse: unused), sum g}: pass the forward's sums, kind and
+ * class_w to the backward.  Everything else (dtype, grad_out, grad_scale, ws, integer scales 2/4/8/16, the fp32 scalar order of the deep-supervision sum) as above. */
+int tcct_softmax_crit_fwd(const void* logits, const uint8_t* labels, int64_t M, int C, int kind, const float* class_w, double* sums, float* loss, int dtype,
+                          tcct_stream_t stream);
+int tcct_softmax_crit_bwd(const void* logits, const uint8_t* labels, int64_t M, int C, int kind, const float* class_w, const double* sums, const float* grad_out,
+                          float grad_scale, void* dlogits, int dtype, tcct_stream_t stream);
+int tcct_upcrit_fwd(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, double* sums, float* loss,
+                    tcct_stream_t stream);
+int tcct_upcrit_bwd(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, const double* sums,
+                    const float* grad_out, float grad_scale, float* ws, float* dlow, tcct_stream_t stream);
+int tcct_crit_ds_fwd(const void* logits, int dtype, const uint8_t* labels, int B, int H, int W, int C, const float* low1, int h1, int w1, const float* low2, int h2, int w2,
+                     const float* low3, int h3, int w3, float coff, int kind, const float* class_w, double* sums, float* loss, tcct_stream_t stream);
 /* softmax prob of the labelled class (regular_udh sort key, nets/reg.py:89) and/or argmax class (KiteSeg.predict,
  * kite/loop_seg.py:32); either output may be NULL */
 int tcct_softmax_pick(const void* logits, const uint8_t* labels, int64_t M, int C, float* prob_lab, uint8_t* argmax,

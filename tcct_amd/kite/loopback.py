@@ -54,10 +54,10 @@ class KiteBack(object):
         """deep supervision, reference loopback.py:62-73: sum_{i=3,2,1} coff_ds*crit(outs[i]) + crit(outs[0])"""
         losSum = 0
         if ds and isinstance(criterion, MultiLoss) and ops.deep_supervision_dice_ok(outs, self.args.coff_ds) and torch.is_grad_enabled():
-            # the whole deep-supervision criterion as one node (same sum, same order, no scalar torch kernels between the Dice kernels)
+            # the whole deep-supervision criterion as one node (same sum, same order, no scalar torch kernels between the criterion kernels), whichever kind
             logits0 = as_nhwc(outs[0])
             if logits0.shape[1:3] == tuple(outs[1].size) and logits0.shape[-1] <= 8:
-                return ops.deep_supervision_dice(logits0, as_label_index(true), list(outs[1:]), self.args.coff_ds)
+                return ops.deep_supervision_criterion(logits0, as_label_index(true), list(outs[1:]), self.args.coff_ds, criterion.kind, criterion.class_w)
         if isinstance(outs, (list, tuple)):
             if ds:
                 for i in range(len(outs) - 1, 0, -1):
@@ -115,4 +115,4 @@ class KiteBack(object):
         self.model = self.model.to(self.device)
         if parallel:
             tdist.broadcast_params_(self.model)
-        self.criterion = get_loss(self.args.los).to(self.device)
+        self.criterion = get_loss(self.args.los, weight=getattr(self.args, 'los_weight', None) or None).to(self.device)

@@ -1,2 +1,2 @@
-from .loss import DiceLoss, MultiLoss, get_loss      # noqa: F401
+from .loss import DiceLoss, IouLoss, MultiLoss, get_loss      # noqa: F401
 from .miou import MDiceLoss, MIouLoss, MaskOneHot    # noqa: F401

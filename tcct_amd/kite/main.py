@@ -2,7 +2,10 @@
 `RegNet(net, con=args.type_udh, out_channels=...)`, `KiteSeg(...).fit(epochs)`.
 
 Additions: `--los=di+reg+fpl` shorthand (BASELINE.json) == `--los=di --reg=true --udh=true`; `--db=synth` synthetic
-GOALS-shaped generator; `--pl=true` = one process per GPU under torchrun; `--dtype=bf16|fp32` compute precision.
+GOALS-shaped generator; `--pl=true` = one process per GPU under torchrun; `--dtype=bf16|fp32` compute precision;
+`--los=d2|iou|mse` name the reference's other per-class criteria (DiceLoss(bi=True), IouLoss, nn.MSELoss; the reference's
+own `get_loss` only reaches Dice and MSE), also inside the shorthand (`--los=iou+reg+fpl`); `--los_weight=1,1,2,2,1` = the
+`weight` list of `MultiLoss` (per-class weights; the reference passes it in code only).
 
     python -m tcct_amd.kite.main --bs=8 --net=stc_tt --los=di --db=synth --epochs=1
 """
@@ -17,6 +20,13 @@ def str2bool(v):
     if v.lower() in ('no', 'false', 'f', 'n', '0'):
         return False
     raise argparse.ArgumentTypeError('Unsupported value encountered.')
+
+
+def float_list(v):
+    try:
+        return [float(q) for q in v.split(',') if q.strip() != '']
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'comma-separated floats expected, got {v!r}')
 
 
 def build_parser():
@@ -48,6 +58,8 @@ def build_parser():
     p.add_argument('--att', type=str, default='pool', choices=['pool', 'factor', 'hydra'],
                    help="token mixer of the ViT blocks: 'pool' = MetaPool (reference nets/tcct.py:449); 'factor' / 'hydra' = the factorised attention / "
                         "HydraAttention the reference keeps commented out (nets/tcct.py:435-448; --net=stc_tt / tcct only)")
+    p.add_argument('--los_weight', type=float_list, default=[],
+                   help='per-class weights of the criterion, comma-separated (MultiLoss(weight=...)); classes beyond the end of the list are dropped, as in the reference')
     p.add_argument('--graph', type=str2bool, default=False,
                    help='EXPERIMENTAL: replay the training step from a hipGraph (launch-bound crop sizes such as the 256x256 of the reference '
                         'recipe; single process, fixed batch shape).  A capture late in a long process has crashed inside hipGraphLaunch '

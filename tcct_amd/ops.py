@@ -3127,6 +3127,136 @@ class _DeepSupervisionDice(_FastFunction):
         return (d0, None, None, None, None) + tuple(dl)
 
 
+# The criterion family of the reference's MultiLoss (kite/losses/loss.py:9-110): per-class loss `kind` + per-class weights.  kind 'dice' without weights IS the nodes
+# above (the benchmark's path, untouched); everything else runs the tcct_softmax_crit_* / tcct_upcrit_* / tcct_crit_ds_fwd kernels (csrc/crit.hip).
+CRIT_KINDS = {'dice': 0, 'dice2': 1, 'iou': 2, 'mse': 3}
+
+
+def _crit_args(kind, class_w, C, device):
+    """-> (kind code, fp32 [C] weights on `device` or None).  The weights are read by the kernels at run time (a persistent buffer of the caller: graph-capturable)."""
+    if kind not in CRIT_KINDS:
+        raise TcctError(f'criterion kind {kind!r}: one of {sorted(CRIT_KINDS)}')
+    if class_w is not None:
+        if not (torch.is_tensor(class_w) and class_w.dtype == torch.float32 and class_w.dim() == 1 and class_w.numel() >= C and class_w.is_contiguous()
+                and class_w.device == device):
+            raise TcctError(f'class weights: a contiguous fp32 vector of at least {C} entries on {device} is needed')
+    return CRIT_KINDS[kind], class_w
+
+
+class _SoftmaxCrit(_FastFunction):
+    @staticmethod
+    def forward(ctx, logits, labels, kind, class_w):
+        _chk(logits, labels)
+        C = logits.shape[-1]
+        M = logits.numel() // C
+        sums = torch.empty(3 * C, device=logits.device, dtype=torch.float64)
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        lib.softmax_crit_fwd(logits, labels, M, C, kind, class_w, sums, loss, dtype_code(logits.dtype))
+        ctx.save_for_backward(logits, labels, sums)
+        ctx.cfg = (kind, class_w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, sums = ctx.saved_tensors
+        kind, class_w = ctx.cfg
+        C = logits.shape[-1]
+        M = logits.numel() // C
+        g = _as(g, torch.float32)
+        d = torch.empty_like(logits)
+        lib.softmax_crit_bwd(logits, labels, M, C, kind, class_w, sums, g, 1.0, d, dtype_code(logits.dtype))
+        return d, None, None, None
+
+
+class _UpCrit(_FastFunction):
+    """MultiLoss(<kind>, weight)(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits"""
+
+    @staticmethod
+    def forward(ctx, low, labels, H, W, kind, class_w):
+        _chk(low, labels)
+        B, h, w, C = low.shape
+        sums = torch.empty(3 * C, device=low.device, dtype=torch.float64)
+        loss = torch.empty((), device=low.device, dtype=torch.float32)
+        lib.upcrit_fwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, loss)
+        ctx.save_for_backward(low, labels, sums)
+        ctx.cfg = (H, W, kind, class_w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, labels, sums = ctx.saved_tensors
+        B, h, w, C = low.shape
+        H, W, kind, class_w = ctx.cfg
+        g = _as(g, torch.float32)
+        ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
+        d = torch.empty_like(low)
+        lib.upcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, g, 1.0, ws, d)
+        return d, None, None, None, None, None
+
+
+class _DeepSupervisionCrit(_FastFunction):
+    """_DeepSupervisionDice for every criterion kind / class weights: one memset, up to four sums kernels, one finalisation"""
+
+    @staticmethod
+    def forward(ctx, logits0, labels, coff, H, W, kind, class_w, *lows):
+        _chk(logits0, labels, *lows)
+        B, _, _, C = logits0.shape
+        sums = torch.empty(4 * 3 * C, device=logits0.device, dtype=torch.float64)
+        loss = torch.empty((), device=logits0.device, dtype=torch.float32)
+        a = []
+        for i in range(3):
+            a += [lows[i], lows[i].shape[1], lows[i].shape[2]] if i < len(lows) else [None, 0, 0]
+        lib.crit_ds_fwd(logits0, dtype_code(logits0.dtype), labels, B, H, W, C, *a, coff, kind, class_w, sums, loss)
+        ctx.save_for_backward(logits0, labels, sums, *lows)
+        ctx.cfg = (coff, H, W, kind, class_w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits0, labels, sums, *lows = ctx.saved_tensors
+        coff, H, W, kind, class_w = ctx.cfg
+        B, _, _, C = logits0.shape
+        g = _as(g, torch.float32)
+        d0 = torch.empty_like(logits0)
+        lib.softmax_crit_bwd(logits0, labels, logits0.numel() // C, C, kind, class_w, sums[:3 * C], g, 1.0, d0, dtype_code(logits0.dtype))
+        dl = []
+        for i, low in enumerate(lows):
+            _, h, w, _ = low.shape
+            ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
+            d = torch.empty_like(low)
+            lib.upcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums[(i + 1) * 3 * C:(i + 2) * 3 * C], g, coff, ws, d)
+            dl.append(d)
+        return (d0, None, None, None, None, None, None) + tuple(dl)
+
+
+def softmax_criterion(logits, labels, kind='dice', class_w=None):
+    """MultiLoss(<kind>, weight): logits NHWC [N,H,W,C], labels uint8 [N,H,W] -> scalar sum_c class_w[c] * L_c.  kind: 'dice' | 'dice2' | 'iou' | 'mse' (the latter is
+    nn.MSELoss against the FLOAT one-hot, per class a mean over all N*H*W pixels); class_w: fp32 device vector [>= C] or None (all ones)."""
+    if kind == 'dice' and class_w is None:
+        return _SoftmaxDice.apply(logits, labels)
+    code, class_w = _crit_args(kind, class_w, logits.shape[-1], logits.device)
+    return _SoftmaxCrit.apply(logits, labels, code, class_w)
+
+
+def softmax_criterion_upsampled(lr, labels, kind='dice', class_w=None):
+    """the criterion of a LowResLogits head"""
+    if kind == 'dice' and class_w is None:
+        return softmax_dice_upsampled(lr, labels)
+    if not lr.fusable():
+        return softmax_criterion(bilinear(lr.low, lr.size, False), labels, kind, class_w)
+    code, class_w = _crit_args(kind, class_w, lr.low.shape[-1], lr.low.device)
+    return _UpCrit.apply(lr.low, labels, lr.size[0], lr.size[1], code, class_w)
+
+
+def deep_supervision_criterion(logits0_nhwc, labels, lows, coff, kind='dice', class_w=None):
+    """deep_supervision_dice for every kind / class weights (same gate: deep_supervision_dice_ok)"""
+    if kind == 'dice' and class_w is None:
+        return deep_supervision_dice(logits0_nhwc, labels, lows, coff)
+    code, class_w = _crit_args(kind, class_w, logits0_nhwc.shape[-1], logits0_nhwc.device)
+    H, W = lows[0].size
+    return _DeepSupervisionCrit.apply(logits0_nhwc, labels, float(coff), H, W, code, class_w, *[l_.low for l_ in lows])
+
+
 DS_DICE_FUSE = True        # False: one criterion node per head + torch scalar arithmetic (A/B timing)
 
 
