@@ -525,6 +525,18 @@ int tcct_l2norm_bwd_scaled_add(const void* x, const void* dy, const void* res, v
  * inv1 / inv2: fp32 workspaces [N*h1*w1] / [N*h2*w2] (the coarse maps' inverse norms, written by a small pre-pass) */
 int tcct_normadd_fwd(const void* g0, const void* g1, const void* g2, float* inv1, float* inv2, void* out, int N, int H, int W, int C,
                      int h1, int w1, int h2, int w2, float eps, int dtype, tcct_stream_t stream);
+/* six-map norm_add of the legacy head layout (task1/onnx/tcct_goals.py:944-947, call site :1024 `self.feats = norm_add([x1,x2,x3,y0,y1,y2])`):
+ * out = (l2n(a0) + l2n(b0) + resize(l2n(a1) + l2n(b1)) + resize(l2n(a2) + l2n(b2))) / 6, bilinear, align_corners=False, one pass over a0 / b0 / out.
+ * The two maps of a level are normalised and added BEFORE the (linear) resize; the reference sums its list left to right, so the association
+ * differs -- fp32 round-off only.  C == 32, H == 2*h1 == 4*h2, H % 8 == 0 (bands of eight rows); anything else is an error (the caller composes
+ * it from the ops above).  inv1 / inv2: fp32 workspaces [2*N*h1*w1] / [2*N*h2*w2] (inverse norms of the a map, then of the b map). */
+int tcct_normadd6_fwd(const void* a0, const void* b0, const void* a1, const void* b1, const void* a2, const void* b2, float* inv1, float* inv2,
+                      void* out, int N, int H, int W, int C, int h1, int w1, int h2, int w2, float eps, int dtype, tcct_stream_t stream);
+/* backward of one level's pair of the six-map norm_add: both maps receive the same incoming gradient dn (dy at level 0, ONE tcct_bilinear_bwd
+ * at levels 1 / 2), read once: da = scale * l2norm_bwd(xa, dn) (+ res_a), db = scale * l2norm_bwd(xb, dn) (+ res_b); res_a / res_b nullable.
+ * Per map bit-identical to tcct_l2norm_bwd_scaled / _scaled_add. */
+int tcct_l2norm_bwd2_scaled(const void* xa, const void* xb, const void* dn, const void* res_a, const void* res_b, void* da, void* db,
+                            int64_t M, int C, float eps, float scale, int dtype, tcct_stream_t stream);
 
 /* ---- MultiLoss(DiceLoss) (kite/losses/loss.py:83-99,15-32): softmax over C fused with the batch-global sums
  * sums[3][C] = {sum p*g, sum p, sum g}; loss = sum_c 1 - (1+2I)/(1+P+G).  labels: class index uint8 [M] ----- */
@@ -626,6 +638,11 @@ int tcct_l2norm_bwd_fplgrad(const void* x, const uint8_t* labels, const uint8_t*
                             float grad_scale, int ncls, const void* res, void* dx, int64_t M, float eps, float scale, int dtype, tcct_stream_t stream);
 int tcct_bilinear_bwd_fplgrad(const uint8_t* labels, const uint8_t* binmap, const float* dpro_over_n, const float* grad_out, float grad_scale, int ncls,
                               void* dx, int N, int H, int W, int Ho, int Wo, int align_corners, int dtype, tcct_stream_t stream);
+/* the level-0 pair of the six-map norm_add (tcct_goals.py:1024) under the feature-polarization gradient: tcct_l2norm_bwd_fplgrad for two maps with
+ * ONE table lookup per pixel; xa, xb, res_a, res_b (nullable), da, db [M,32] */
+int tcct_l2norm_bwd2_fplgrad(const void* xa, const void* xb, const uint8_t* labels, const uint8_t* binmap, const float* dpro_over_n,
+                             const float* grad_out, float grad_scale, int ncls, const void* res_a, const void* res_b, void* da, void* db,
+                             int64_t M, float eps, float scale, int dtype, tcct_stream_t stream);
 
 /* ---- factorised attention with convolutional relative position encoding: FactorAtt_ConvRelPosEnc.forward
  * nets/tcct.py:311-341 and ConvRelPosEnc.forward nets/tcct.py:265-287, the token mixer the reference keeps commented out in MHCABlock

@@ -1111,3 +1111,202 @@ extern "C" int tcct_normadd_fwd(const void* g0, const void* g1, const void* g2, 
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_normadd_fwd<T>, row_grid(W * LP, ((int64_t)N * H + NA_ROWS - 1) / NA_ROWS, 8192), dim3(PB), 0, st, (const T*)g0, (const T*)g1, (const T*)g2, inv1, inv2, (T*)out, N, H, W, C, h1, w1, h2, w2, eps));
     TCCT_LAUNCH_OK();
 }
+
+// ------------------------------------------------- six-map norm_add of the legacy head layout (reference task1/onnx/tcct_goals.py:944-947,1024)
+// feats = norm_add([x1, x2, x3, y0, y1, y2]): the mean of SIX L2-normalised maps, two per resolution (encoder skip + decoder output at full, half and
+// quarter size), 32 channels each.  The resize is linear and the two maps of a level share the resolution, so
+//     resize(l2n(a)) + resize(l2n(b)) = resize(l2n(a) + l2n(b)):
+// the pair is normalised and ADDED at the coarse pixel, and the sum is interpolated once -- the blend work per output pixel is that of the three-map
+// kernel.  Band form only (H == 2 h1 == 4 h2, H % 8 == 0, the network's case); other shapes are composed from existing ops by the caller.
+// Association: ((l2n(a0) + l2n(b0)) + resize(pair 1) + resize(pair 2)) / 6 where the reference sums its list left to right -- fp32 round-off only.
+template <typename T>
+__global__ void k_normadd6_fwd_band(const T* __restrict__ a0, const T* __restrict__ b0, const T* __restrict__ a1, const T* __restrict__ b1,
+                                    const T* __restrict__ a2, const T* __restrict__ b2, const float* __restrict__ inv1, const float* __restrict__ inv2,
+                                    T* __restrict__ out, int N, int H, int W, int h1, int w1, int h2, int w2, float eps) {
+    const int C = 32, LP = 8;
+    const unsigned lb = xcd_band(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    const int bx = (int)(lb % gridDim.x), by = (int)(lb / gridDim.x);
+    const int i = bx * blockDim.x + threadIdx.x;            // blockDim.x is a multiple of 64 -> the eight lanes of a pixel stay inside a wave
+    const bool ok = i < W * LP;
+    const int wo = ok ? i / LP : 0, c = ok ? (i - wo * LP) * 4 : 0;
+    const Lerp l1 = src_index(wo, (float)w1 / (float)W, w1, 0), l2 = src_index(wo, (float)w2 / (float)W, w2, 0);
+    const int64_t M1 = (int64_t)N * h1 * w1, M2 = (int64_t)N * h2 * w2;       // inv1 / inv2 hold [2][M]: the a map's inverse norms, then the b map's
+    const int bands = H >> 3;
+    for (int band = by; band < N * bands; band += gridDim.y) {
+        const int n = band / bands, kb = band - n * bands;
+        f4 hx1[6], hx2[4];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const int row = min(max(4 * kb - 1 + j, 0), h1 - 1);
+            const int64_t r0 = ((int64_t)n * h1 + row) * w1;
+            const f4 xa0 = ld4(a1 + (r0 + l1.i0) * C + c), xa1 = ld4(a1 + (r0 + l1.i1) * C + c);
+            const f4 xb0 = ld4(b1 + (r0 + l1.i0) * C + c), xb1 = ld4(b1 + (r0 + l1.i1) * C + c);
+            const float ia0 = inv1[r0 + l1.i0], ia1 = inv1[r0 + l1.i1], ib0 = inv1[M1 + r0 + l1.i0], ib1 = inv1[M1 + r0 + l1.i1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) hx1[j].v[k] = l1.l0 * (xa0.v[k] * ia0 + xb0.v[k] * ib0) + l1.l1 * (xa1.v[k] * ia1 + xb1.v[k] * ib1);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = min(max(2 * kb - 1 + j, 0), h2 - 1);
+            const int64_t r0 = ((int64_t)n * h2 + row) * w2;
+            const f4 xa0 = ld4(a2 + (r0 + l2.i0) * C + c), xa1 = ld4(a2 + (r0 + l2.i1) * C + c);
+            const f4 xb0 = ld4(b2 + (r0 + l2.i0) * C + c), xb1 = ld4(b2 + (r0 + l2.i1) * C + c);
+            const float ia0 = inv2[r0 + l2.i0], ia1 = inv2[r0 + l2.i1], ib0 = inv2[M2 + r0 + l2.i0], ib1 = inv2[M2 + r0 + l2.i1];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) hx2[j].v[k] = l2.l0 * (xa0.v[k] * ia0 + xb0.v[k] * ib0) + l2.l1 * (xa1.v[k] * ia1 + xb1.v[k] * ib1);
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int ho = 8 * kb + r;
+            const int64_t row = (int64_t)n * H + ho;
+            const f4 va = ld4(a0 + (row * W + wo) * C + c), vb = ld4(b0 + (row * W + wo) * C + c);
+            float sa = va.v[0] * va.v[0] + va.v[1] * va.v[1] + va.v[2] * va.v[2] + va.v[3] * va.v[3];
+            float sb = vb.v[0] * vb.v[0] + vb.v[1] * vb.v[1] + vb.v[2] * vb.v[2] + vb.v[3] * vb.v[3];
+            sa = lane_group_sum(sa, LP);
+            sb = lane_group_sum(sb, LP);
+            const float ida = 1.f / fmaxf(sqrtf(sa), eps), idb = 1.f / fmaxf(sqrtf(sb), eps);
+            const Lerp v1 = src_index(ho, (float)h1 / (float)H, h1, 0), v2 = src_index(ho, (float)h2 / (float)H, h2, 0);
+            const f4 &p0 = hx1[(r + 1) >> 1], &p1 = hx1[((r + 1) >> 1) + 1], &q0 = hx2[(r + 2) >> 2], &q1 = hx2[((r + 2) >> 2) + 1];
+            f4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float t = (va.v[k] * ida + vb.v[k] * idb) + (v1.l0 * p0.v[k] + v1.l1 * p1.v[k]);
+                o.v[k] = (t + (v2.l0 * q0.v[k] + v2.l1 * q1.v[k])) * (1.f / 6.f);
+            }
+            if (ok) st4(out + (row * W + wo) * C + c, o);
+        }
+    }
+}
+/* a0, b0 [N,H,W,32]; a1, b1 [N,h1,w1,32]; a2, b2 [N,h2,w2,32] -> out [N,H,W,32]; inv1 / inv2: fp32 workspaces [2*N*h1*w1] / [2*N*h2*w2] (written here) */
+extern "C" int tcct_normadd6_fwd(const void* a0, const void* b0, const void* a1, const void* b1, const void* a2, const void* b2, float* inv1, float* inv2,
+                                 void* out, int N, int H, int W, int C, int h1, int w1, int h2, int w2, float eps, int dtype, tcct_stream_t stream) {
+    TCCT_CHECK(C == 32, "normadd6_fwd: C=%d unsupported (32 only)", C);
+    TCCT_CHECK(N >= 1 && W >= 1 && h1 >= 1 && w1 >= 1 && h2 >= 1 && w2 >= 1 && inv1 && inv2, "normadd6_fwd: bad shapes / NULL workspace");
+    TCCT_CHECK(H == 2 * h1 && H == 4 * h2 && H % 8 == 0, "normadd6_fwd: needs H == 2*h1 == 4*h2 and H %% 8 == 0 (got %d, %d, %d)", H, h1, h2);
+    TCCT_CHECK((int64_t)W * 8 < 0x7fffffffLL && (int64_t)N * (H / 8) < 0x7fffffffLL, "normadd6_fwd: shape too large");
+    hipStream_t st = (hipStream_t)stream;
+    const int LP = 8;
+    const int64_t M1 = (int64_t)N * h1 * w1, M2 = (int64_t)N * h2 * w2;
+    TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_invnorm<T>, dim3(tcct_grid(M1 * LP, PB, 1 << 16)), dim3(PB), 0, st, (const T*)a1, inv1, M1, C, eps));
+    TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_invnorm<T>, dim3(tcct_grid(M1 * LP, PB, 1 << 16)), dim3(PB), 0, st, (const T*)b1, inv1 + M1, M1, C, eps));
+    TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_invnorm<T>, dim3(tcct_grid(M2 * LP, PB, 1 << 16)), dim3(PB), 0, st, (const T*)a2, inv2, M2, C, eps));
+    TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_invnorm<T>, dim3(tcct_grid(M2 * LP, PB, 1 << 16)), dim3(PB), 0, st, (const T*)b2, inv2 + M2, M2, C, eps));
+    TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_normadd6_fwd_band<T>, row_grid(W * LP, (int64_t)N * (H / 8), 8192), dim3(PB), 0, st, (const T*)a0, (const T*)b0,
+                                            (const T*)a1, (const T*)b1, (const T*)a2, (const T*)b2, inv1, inv2, (T*)out, N, H, W, h1, w1, h2, w2, eps));
+    TCCT_LAUNCH_OK();
+}
+
+// backward of one level's PAIR: the two maps of a level receive the SAME incoming gradient dn (dy itself at level 0, one tcct_bilinear_bwd at levels
+// 1 / 2), so dn is read once and both input gradients are written.  Per map the arithmetic is k_l2norm<T, true>'s, expression for expression.
+template <typename T>
+__global__ void k_l2norm_bwd2(const T* __restrict__ xa, const T* __restrict__ xb, const T* __restrict__ dn, const T* __restrict__ resa,
+                              const T* __restrict__ resb, T* __restrict__ outa, T* __restrict__ outb, int64_t M, int C, float eps, float oscale) {
+    const int LP = C >> 2;
+    const int64_t total = M * LP;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;     // multiple of 64 -> lanes of a pixel stay together
+    const int64_t rounds = (total + stride - 1) / stride;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t it = 0; it < rounds; ++it, i += stride) {
+        const bool ok = i < total;
+        const int64_t ii = ok ? i : 0;
+        const f4 g = ld4(dn + ii * 4);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const T* x = m ? xb : xa;
+            const T* res = m ? resb : resa;
+            T* out = m ? outb : outa;
+            const f4 v = ld4(x + ii * 4);
+            // the two four-term sums with their fused multiply-adds spelled out: `a*a + b*b + ...` leaves the compiler free to choose WHICH product of
+            // the first pair is rounded on its own, and it chose differently here than in k_l2norm<T, true> (1 ulp apart).  This is k_l2norm's choice.
+            float ss = __builtin_fmaf(v.v[3], v.v[3], __builtin_fmaf(v.v[2], v.v[2], __builtin_fmaf(v.v[0], v.v[0], v.v[1] * v.v[1])));
+            float dot = __builtin_fmaf(v.v[3], g.v[3], __builtin_fmaf(v.v[2], g.v[2], __builtin_fmaf(v.v[1], g.v[1], v.v[0] * g.v[0])));
+            for (int o = LP >> 1; o > 0; o >>= 1) { ss += __shfl_xor(ss, o, 64); dot += __shfl_xor(dot, o, 64); }
+            const float nrm = sqrtf(ss);
+            const float d = fmaxf(nrm, eps);
+            const float coef = nrm > eps ? dot / (d * d * nrm) : 0.f;
+            f4 r;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r.v[k] = oscale * (g.v[k] / d - v.v[k] * coef);
+            if (res) {
+                const f4 e = ld4(res + ii * 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r.v[k] += e.v[k];
+            }
+            if (ok) st4(out + ii * 4, r);
+        }
+    }
+}
+/* da = scale * l2norm_bwd(xa, dn) (+ res_a), db = scale * l2norm_bwd(xb, dn) (+ res_b); xa, xb, dn, res_*, da, db [M,C]; res_a / res_b nullable */
+extern "C" int tcct_l2norm_bwd2_scaled(const void* xa, const void* xb, const void* dn, const void* res_a, const void* res_b, void* da, void* db,
+                                       int64_t M, int C, float eps, float scale, int dtype, tcct_stream_t stream) {
+    const int LP = C / 4;
+    TCCT_CHECK(C % 4 == 0 && LP >= 1 && LP <= 64 && (LP & (LP - 1)) == 0, "l2norm_bwd2_scaled: C=%d unsupported", C);
+    TCCT_CHECK(xa && xb && dn && da && db && da != db && M >= 1, "l2norm_bwd2_scaled: NULL / aliased tensors");
+    TCCT_CHECK((res_a == nullptr || (res_a != da && res_a != db)) && (res_b == nullptr || (res_b != da && res_b != db)),
+               "l2norm_bwd2_scaled: res must be separate tensors");
+    TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_l2norm_bwd2<T>, dim3(tcct_grid(M * LP, PB, 1 << 16)), dim3(PB), 0, (hipStream_t)stream, (const T*)xa, (const T*)xb,
+                                            (const T*)dn, (const T*)res_a, (const T*)res_b, (T*)da, (T*)db, M, C, eps, scale));
+    TCCT_LAUNCH_OK();
+}
+
+// the level-0 pair when dn is the feature-polarization gradient: the table row of (label, bin) is looked up ONCE per pixel and used for both maps
+// (k_l2norm_bwd_fplgrad's arithmetic per map; C = 32: eight lanes per pixel)
+template <typename T>
+__global__ void k_l2norm_bwd2_fplgrad(const T* __restrict__ xa, const T* __restrict__ xb, const uint8_t* __restrict__ lab, const uint8_t* __restrict__ binmap,
+                                      const float* __restrict__ dpro, const float* __restrict__ gout, float gscale, int ncls, const T* __restrict__ resa,
+                                      const T* __restrict__ resb, T* __restrict__ outa, T* __restrict__ outb, int64_t M, float eps, float oscale) {
+    extern __shared__ float stab[];         // [ncls][32][32]
+    for (int i = threadIdx.x; i < ncls * FG_BINS * 32; i += blockDim.x) stab[i] = dpro[i];
+    __syncthreads();
+    const float gs = gscale * (gout ? *gout : 1.f);
+    const int64_t total = M * 8;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t rounds = (total + stride - 1) / stride;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t it = 0; it < rounds; ++it, i += stride) {
+        const bool ok = i < total;
+        const int64_t ii = ok ? i : 0, p = ii >> 3;
+        const int sub = (int)(ii & 7);
+        const int b = binmap[p], l = lab[p];
+        f4 g = f4zero();
+        if (b < FG_BINS && l < ncls) {
+            const float* d = stab + (l * FG_BINS + b) * 32 + sub * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g.v[k] = round_as<T>(gs * d[k]);
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const T* x = m ? xb : xa;
+            const T* res = m ? resb : resa;
+            T* out = m ? outb : outa;
+            const f4 v = ld4(x + ii * 4);
+            float ss = v.v[0] * v.v[0] + v.v[1] * v.v[1] + v.v[2] * v.v[2] + v.v[3] * v.v[3];
+            float dot = v.v[0] * g.v[0] + v.v[1] * g.v[1] + v.v[2] * g.v[2] + v.v[3] * g.v[3];
+            for (int o = 4; o > 0; o >>= 1) { ss += __shfl_xor(ss, o, 64); dot += __shfl_xor(dot, o, 64); }
+            const float nrm = sqrtf(ss), dn = fmaxf(nrm, eps);
+            const float coef = nrm > eps ? dot / (dn * dn * nrm) : 0.f;
+            f4 r;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r.v[k] = oscale * (g.v[k] / dn - v.v[k] * coef);
+            if (res) {
+                const f4 e = ld4(res + ii * 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) r.v[k] += e.v[k];
+            }
+            if (ok) st4(out + ii * 4, r);
+        }
+    }
+}
+/* da / db = scale * l2norm_bwd(xa / xb, dfeat) (+ res_a / res_b, nullable), dfeat looked up from (labels, binmap, dpro_over_n [ncls][32][32]); [M,32] */
+extern "C" int tcct_l2norm_bwd2_fplgrad(const void* xa, const void* xb, const uint8_t* labels, const uint8_t* binmap, const float* dpro_over_n,
+                                        const float* grad_out, float grad_scale, int ncls, const void* res_a, const void* res_b, void* da, void* db,
+                                        int64_t M, float eps, float scale, int dtype, tcct_stream_t stream) {
+    TCCT_CHECK(ncls >= 1 && ncls <= 16 && labels && binmap && dpro_over_n, "l2norm_bwd2_fplgrad: bad arguments (ncls=%d)", ncls);
+    TCCT_CHECK(xa && xb && da && db && da != db && M >= 1, "l2norm_bwd2_fplgrad: NULL / aliased tensors");
+    const size_t lds = sizeof(float) * (size_t)ncls * FG_BINS * 32;
+    TCCT_DISPATCH(dtype, {
+        tcct_launch<k_l2norm_bwd2_fplgrad<T>, 80 * 1024>(dim3(tcct_grid(M * 8, PB, 2048)), dim3(PB), lds, (hipStream_t)stream, (const T*)xa, (const T*)xb, labels,
+                                                         binmap, dpro_over_n, grad_out, grad_scale, ncls, (const T*)res_a, (const T*)res_b, (T*)da, (T*)db, M,
+                                                         eps, scale); });
+    TCCT_LAUNCH_OK();
+}

@@ -58,6 +58,9 @@ def build_parser():
     p.add_argument('--att', type=str, default='pool', choices=['pool', 'factor', 'hydra'],
                    help="token mixer of the ViT blocks: 'pool' = MetaPool (reference nets/tcct.py:449); 'factor' / 'hydra' = the factorised attention / "
                         "HydraAttention the reference keeps commented out (nets/tcct.py:435-448; --net=stc_tt / tcct only)")
+    p.add_argument('--legacy_heads', type=str2bool, default=False,
+                   help='older head layout of the reference\'s shipped GOALS / HCMS / HEG checkpoints (task1/onnx/tcct_goals.py: no t32x convolutions, '
+                        'six-map feats; --net=stc_tt / tcct only)')
     p.add_argument('--los_weight', type=float_list, default=[],
                    help='per-class weights of the criterion, comma-separated (MultiLoss(weight=...)); classes beyond the end of the list are dropped, as in the reference')
     p.add_argument('--graph', type=str2bool, default=False,
@@ -79,6 +82,8 @@ def parse_args(argv=None):
                 args.udh = True
             else:
                 raise SystemExit(f'unknown loss component {q!r} in --los')
+    if args.legacy_heads and args.net not in ('stc_tt', 'tcct'):
+        raise SystemExit('--legacy_heads=true is only offered for --net=stc_tt')
     return args
 
 
@@ -96,6 +101,8 @@ def main(argv=None):
         if args.net not in ('stc_tt', 'tcct'):
             raise SystemExit(f'--att={args.att} is only offered for --net=stc_tt')
         kw['att'] = args.att
+    if args.legacy_heads:
+        kw['legacy_heads'] = True
     net = factory(dataset.out_channels, **kw)
     net = nets.RegNet(net, con=args.type_udh, out_channels=dataset.out_channels)
     keras = KiteSeg(model=net, dataset=dataset, root=args.root, args=args)

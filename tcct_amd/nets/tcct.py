@@ -697,12 +697,14 @@ class FTC(nn.Module):
 
     @property
     def feats(self):
-        """[norm_add([y0, y1, y2])] (reference tcct.py:1035).  Inside a pooled training step the feature-polarization loss sends its gradient towards `feats` as a
+        """[norm_add([y0, y1, y2])] (reference tcct.py:1035; legacy_heads: [norm_add([x1, x2, x3, y0, y1, y2])], onnx/tcct_goals.py:1024).  Inside a pooled training step the feature-polarization loss sends its gradient towards `feats` as a
         recipe, not as a tensor (ops.grad_is_watched documents who still sees the dense d loss / d feats: retain_grad() / hooks set BEFORE the loss is formed)."""
         if self._feats is None and self._feats_src is not None:
-            if self.legacy_heads:
-                raise TcctError('the legacy-head layout (onnx/tcct_goals.py) is supported for inference and Dice/boundary training; its '
-                                'six-tensor `feats` (tcct_goals.py:1021) is not built')
+            if self.legacy_heads:       # tcct_goals.py:1024: norm_add([x1, x2, x3, y0, y1, y2]), the two maps of a level side by side
+                x1, x2, x3, y0, y1, y2 = self._feats_src[0]
+                self._feats = [_nchw_view(ops.norm_add6(x1, y0, x2, y1, x3, y2))]
+                self._feats_src = None
+                return self._feats
             g0, g1, g2, size = self._feats_src
             # a step with `compose_heads` composed a head through its t32x convolution and never wrote g_i: rebuild it (no gradient -- the owner's promise)
             g0, g1, g2 = [g() if callable(g) else g for g in (g0, g1, g2)]
@@ -827,8 +829,10 @@ class FTC(nn.Module):
             g1, g2, g3 = mids
         # norm_add([y0,y1,y2]) (reference tcct.py:937-942,1035) -> `self.feats`: evaluated lazily on first access (only the
         # feature-polarization loss reads it; with --udh=false the six level-0 passes are simply never launched)
-        self._feats_src = (g0, g1, g2, size)
+        self._feats_src = ((f[0], f[1], f[2], g0, g1, g2), size) if self.legacy_heads else (g0, g1, g2, size)
         self._feats = None
+        if self.eager_feats and self.legacy_heads and not mho:
+            _ = self.feats          # six-map norm_add (ops.norm_add6); the other consumers' gradients of the six maps are accumulated by autograd
         if self.eager_feats and not self.legacy_heads and not mho:
             # the loss WILL read `feats` (KiteSeg sets the flag with --udh): evaluate norm_add here and let the aux heads read aliases of g0..g2
             # returned by its node, so that the heads' gradients are added inside norm_add's backward kernels (three accumulation passes fewer)

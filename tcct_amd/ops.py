@@ -3035,6 +3035,95 @@ def norm_add3_fork(g0, g1, g2, eps=1e-12):
     return _NormAdd.apply(g0, g1, g2, float(eps), True)
 
 
+class _NormAdd6(_FastFunction):
+    """norm_add([x1, x2, x3, y0, y1, y2]) of the legacy head layout (reference task1/onnx/tcct_goals.py:944-947,1024): the mean of six L2-normalised
+    maps, two per resolution.  Forward: one pass (tcct_normadd6_fwd; each coarse pair is normalised and added before its one resize).  Backward: the
+    two maps of a level share their incoming gradient -- dy at level 0, ONE resize gradient per coarse level -- which tcct_l2norm_bwd2_scaled reads
+    once for both, the 1/6 folded in.  Takes part in the lazy feature-polarization gradient exactly as _NormAdd does."""
+
+    @staticmethod
+    def forward(ctx, a0, b0, a1, b1, a2, b2, eps):
+        ctx.set_materialize_grads(False)
+        _chk(a0, b0, a1, b1, a2, b2)
+        N, H, W, C = a0.shape
+        (_, h1, w1, _), (_, h2, w2, _) = a1.shape, a2.shape
+        out = torch.empty_like(a0)
+        inv1 = torch.empty(2 * N * h1 * w1, device=a0.device, dtype=torch.float32)
+        inv2 = torch.empty(2 * N * h2 * w2, device=a0.device, dtype=torch.float32)
+        lib.normadd6_fwd(a0, b0, a1, b1, a2, b2, inv1, inv2, out, N, H, W, C, h1, w1, h2, w2, eps, dtype_code(a0.dtype))
+        ctx.save_for_backward(a0, b0, a1, b1, a2, b2)
+        ctx.eps = eps
+        ctx.out_ptr = out.data_ptr()
+        _FPL_LAZY['producers'].add(out.data_ptr())
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        xs = ctx.saved_tensors
+        a0 = xs[0]
+        pending = _FPL_LAZY['pending'].pop(ctx.out_ptr, [])        # recipes of every _Fpl node that consumed THIS node's output
+        if dy is None and not pending:
+            return (None,) * 7
+        N, H, W, C = a0.shape
+        dc = dtype_code(a0.dtype)
+        lazy = None
+        if dy is not None and len(pending) == 1 and dy.dim() == 4 and dy.stride(0) == 0 and dy.data_ptr() == pending[0][0].data_ptr():
+            lazy = _FPL_LAZY['grads'].pop(dy.data_ptr(), None)     # the single placeholder, untouched by autograd
+        elif pending:
+            # autograd ADDED the placeholder(s) to another gradient (or to each other): the dense sum lacks the FPL part -- materialise it
+            dy = None if dy is None else _c(_as(dy, a0.dtype))
+            for marker, labels, binmap, dpro, gup, ncls in pending:
+                _FPL_LAZY['grads'].pop(marker.data_ptr(), None)
+                dfeat = torch.empty_like(a0)
+                lib.fpl_backward(labels, binmap, dpro, gup, 1.0, int(labels.numel()), dfeat, dc)
+                dy = dfeat if dy is None else add(dy, dfeat)
+        if lazy is None:
+            dy = _c(_as(dy, a0.dtype))
+        outs = []
+        for a, b in ((xs[0], xs[1]), (xs[2], xs[3]), (xs[4], xs[5])):
+            h, w = a.shape[1], a.shape[2]
+            da, db = torch.empty_like(a), torch.empty_like(b)
+            M = a.numel() // C
+            if lazy is not None and (h, w) == (H, W):       # the gradient is the feature-polarization loss's: looked up, never materialised
+                _, labels, binmap, dpro, gup, ncls = lazy
+                lib.l2norm_bwd2_fplgrad(a, b, labels, binmap, dpro, gup, 1.0, ncls, None, None, da, db, M, ctx.eps, 1.0 / 6.0, dc)
+            else:
+                if (h, w) == (H, W):
+                    dn = dy
+                else:                                       # ONE resize gradient for the pair
+                    dn = torch.empty_like(a)
+                    if lazy is not None:
+                        _, labels, binmap, dpro, gup, ncls = lazy
+                        lib.bilinear_bwd_fplgrad(labels, binmap, dpro, gup, 1.0, ncls, dn, N, h, w, H, W, 0, dc)
+                    else:
+                        lib.bilinear_bwd(dy, dn, N, h, w, C, H, W, 0, dc)
+                lib.l2norm_bwd2_scaled(a, b, dn, None, None, da, db, M, C, ctx.eps, 1.0 / 6.0, dc)
+            outs += [da, db]
+        return (*outs, None)
+
+
+def norm_add6_fused_ok(a0, b0, a1, b1, a2, b2):
+    """the shapes tcct_normadd6_fwd covers: 32 channels, one dtype, the two maps of a level alike, levels at H, H/2, H/4 with H % 8 == 0"""
+    ts = (a0, b0, a1, b1, a2, b2)
+    if any(t.dim() != 4 or t.shape[-1] != 32 or t.dtype != a0.dtype or t.shape[0] != a0.shape[0] for t in ts):
+        return False
+    if a0.dtype not in (torch.float32, torch.bfloat16) or any(a.shape != b.shape for a, b in ((a0, b0), (a1, b1), (a2, b2))):
+        return False
+    H = a0.shape[1]
+    return H % 8 == 0 and H == 2 * a1.shape[1] == 4 * a2.shape[1]
+
+
+def norm_add6(a0, b0, a1, b1, a2, b2, eps=1e-12):
+    """norm_add of six maps, two per level (a_i, b_i alike; levels 1 / 2 coarser than level 0): the `feats` of the legacy head layout (reference
+    task1/onnx/tcct_goals.py:1024, in its order [x1, x2, x3, y0, y1, y2] = [a0, a1, a2, b0, b1, b2]).  Fused for 32 channels at H, H/2, H/4 with
+    H % 8 == 0; every other case is composed from l2norm / add / bilinear (the same values up to round-off)."""
+    if norm_add6_fused_ok(a0, b0, a1, b1, a2, b2):
+        return _NormAdd6.apply(a0, b0, a1, b1, a2, b2, float(eps))
+    dt, size = a0.dtype, tuple(a0.shape[1:3])
+    pair = [add(l2norm(_as(a, dt), eps), l2norm(_as(b, dt), eps)) for a, b in ((a0, b0), (a1, b1), (a2, b2))]
+    return add3_scale(pair[0], bilinear(pair[1], size, False), bilinear(pair[2], size, False), 1.0 / 6.0)
+
+
 # ------------------------------------------------------------------------------------------------ losses
 class _SoftmaxDice(_FastFunction):
     @staticmethod
