@@ -28,6 +28,8 @@ enum { TCCT_ACT_NONE = 0, TCCT_ACT_LRELU = 1, TCCT_ACT_HSWISH = 2, TCCT_ACT_GELU
        TCCT_ACT_ABS = 5 };
 /* per-class loss of MultiLoss (tcct_softmax_crit_*, tcct_upcrit_*, tcct_crit_ds_fwd) */
 enum { TCCT_CRIT_DICE = 0, TCCT_CRIT_DICE2 = 1, TCCT_CRIT_IOU = 2, TCCT_CRIT_MSE = 3 };
+/* criteria of get_mloss: per-SAMPLE Dice / IoU and cross-entropy (tcct_softmax_mcrit_*, tcct_upmcrit_*, tcct_mcrit_ds_fwd) */
+enum { TCCT_MCRIT_DICE = 0, TCCT_MCRIT_DICE2 = 1, TCCT_MCRIT_IOU = 2, TCCT_MCRIT_CE = 3 };
 
 int tcct_version(void);
 const char* tcct_last_error(void);
@@ -574,6 +576,22 @@ int tcct_upcrit_bwd(const float* low, const uint8_t* labels, int B, int h, int w
                     const float* grad_out, float grad_scale, float* ws, float* dlow, tcct_stream_t stream);
 int tcct_crit_ds_fwd(const void* logits, int dtype, const uint8_t* labels, int B, int H, int W, int C, const float* low1, int h1, int w1, const float* low2, int h2, int w2,
                      const float* low3, int h3, int w3, float coff, int kind, const float* class_w, double* sums, float* loss, tcct_stream_t stream);
+/* ---- get_mloss (kite/losses/lossm.py over kite/losses/miou.py:46-62,93-117): the five entry points above for the criteria taken per SAMPLE and per class, and for
+ * nn.CrossEntropyLoss(weight).  p = softmax(logits) over C, g = one-hot(label), sums over the HW pixels of ONE sample n:  A = sum pg, P = sum p, G = sum g
+ *   dice   1 - 1/(BC) sum_{n,c} 2 (A + 1e-6) / (P + G + 1e-6)         dice2  dice + the same on the complements (1 - p, 1 - g): A' = HW - P - G + A, P' = HW - P, G' = HW - G
+ *   iou    1 - 1/(BC) sum_{n,c} A / (P + G - A + 1e-6)                ce     sum_{n,c} A / sum_{n,c} G  with  A[l] = sum w_l (-log p_l), G[l] = sum w_l  (slot P unused)
+ * sums fp64 [B][3][C] per head (B = batch: the entry points take B and the pixels per sample HW instead of M).  class_w: device fp32 [C], NULL = all ones, read by ce only.
+ * Everything else (dtype, grad_out, grad_scale, ws, integer scales 2/4/8/16, the fp32 scalar order of the deep-supervision sum, sums of head i at i * B*3C) as above. */
+int tcct_softmax_mcrit_fwd(const void* logits, const uint8_t* labels, int B, int64_t HW, int C, int kind, const float* class_w, double* sums, float* loss, int dtype,
+                           tcct_stream_t stream);
+int tcct_softmax_mcrit_bwd(const void* logits, const uint8_t* labels, int B, int64_t HW, int C, int kind, const float* class_w, const double* sums, const float* grad_out,
+                           float grad_scale, void* dlogits, int dtype, tcct_stream_t stream);
+int tcct_upmcrit_fwd(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, double* sums, float* loss,
+                     tcct_stream_t stream);
+int tcct_upmcrit_bwd(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, const double* sums,
+                     const float* grad_out, float grad_scale, float* ws, float* dlow, tcct_stream_t stream);
+int tcct_mcrit_ds_fwd(const void* logits, int dtype, const uint8_t* labels, int B, int H, int W, int C, const float* low1, int h1, int w1, const float* low2, int h2, int w2,
+                      const float* low3, int h3, int w3, float coff, int kind, const float* class_w, double* sums, float* loss, tcct_stream_t stream);
 /* softmax prob of the labelled class (regular_udh sort key, nets/reg.py:89) and/or argmax class (KiteSeg.predict,
  * kite/loop_seg.py:32); either output may be NULL */
 int tcct_softmax_pick(const void* logits, const uint8_t* labels, int64_t M, int C, float* prob_lab, uint8_t* argmax,

@@ -14,8 +14,9 @@ from torch.optim import lr_scheduler
 from .. import dist as tdist
 from .. import ops
 from ..optim import FlatAdamW
-from .losses import get_loss
+from .losses import get_loss, get_mloss
 from .losses.loss import MultiLoss, as_nhwc, as_label_index
+from .losses.lossm import M_CRITERIA
 
 
 def setup_seed(seed):
@@ -53,10 +54,12 @@ class KiteBack(object):
     def grad_calc(self, outs, true, ds=True, criterion=None):
         """deep supervision, reference loopback.py:62-73: sum_{i=3,2,1} coff_ds*crit(outs[i]) + crit(outs[0])"""
         losSum = 0
-        if ds and isinstance(criterion, MultiLoss) and ops.deep_supervision_dice_ok(outs, self.args.coff_ds) and torch.is_grad_enabled():
+        if ds and isinstance(criterion, (MultiLoss,) + M_CRITERIA) and ops.deep_supervision_dice_ok(outs, self.args.coff_ds) and torch.is_grad_enabled():
             # the whole deep-supervision criterion as one node (same sum, same order, no scalar torch kernels between the criterion kernels), whichever kind
             logits0 = as_nhwc(outs[0])
             if logits0.shape[1:3] == tuple(outs[1].size) and logits0.shape[-1] <= 8:
+                if isinstance(criterion, M_CRITERIA):       # the get_mloss family: per-sample Dice / IoU, cross-entropy
+                    return ops.deep_supervision_mcriterion(logits0, as_label_index(true), list(outs[1:]), self.args.coff_ds, criterion.kind, criterion.class_w)
                 return ops.deep_supervision_criterion(logits0, as_label_index(true), list(outs[1:]), self.args.coff_ds, criterion.kind, criterion.class_w)
         if isinstance(outs, (list, tuple)):
             if ds:
@@ -115,4 +118,6 @@ class KiteBack(object):
         self.model = self.model.to(self.device)
         if parallel:
             tdist.broadcast_params_(self.model)
-        self.criterion = get_loss(self.args.los, weight=getattr(self.args, 'los_weight', None) or None).to(self.device)
+        weight = getattr(self.args, 'los_weight', None) or None
+        mlos = getattr(self.args, 'mlos', '')               # --mlos: the reference's second factory (kite/losses/lossm.py) in place of get_loss
+        self.criterion = (get_mloss(mlos, weight=weight) if mlos else get_loss(self.args.los, weight=weight)).to(self.device)

@@ -1,4 +1,6 @@
-"""Validation metrics — mirror of the static scorers of reference kite/losses/miou.py:28-44,69-91.
+"""Validation metrics — mirror of the static scorers of reference kite/losses/miou.py:28-44,69-91 — and the training criteria of the same classes
+(`forward`, miou.py:46-62,93-117: Dice / IoU per SAMPLE and per class, selected by kite/losses/lossm.py::get_mloss), on the tcct_softmax_mcrit_* /
+tcct_upmcrit_* kernels.
 
 `pr` is either the one-hot mask tensor [B,C,H,W] returned by `KiteSeg.predict` (a lazy `MaskOneHot`), or any tensor whose
 argmax over dim 1 is the class; `gt` one-hot [B,C,H,W] or class indices [B,H,W].  Counting runs in one HIP kernel
@@ -6,8 +8,9 @@ argmax over dim 1 is the class; `gt` one-hot [B,C,H,W] or class indices [B,H,W].
 import torch
 from torch import nn
 
+from ... import ops
 from ..._lib import lib, TcctError
-from ...nets.reg import as_label_index
+from ...nets.reg import as_label_index, as_nhwc
 
 
 def _counts(pr, gt):
@@ -48,7 +51,26 @@ class MaskOneHot:
         return out
 
 
+def _mforward(self, pr, gt):
+    """criterion(logits [B,C,H,W] (dense NCHW view) | ops.LowResLogits, one-hot [B,C,H,W] | class indices [B,H,W]) -> scalar"""
+    if isinstance(pr, ops.LowResLogits):        # deep-supervision head before its resize: fused resize + softmax + criterion
+        return ops.softmax_mcriterion_upsampled(pr, as_label_index(gt), self.kind, self.class_w)
+    return ops.softmax_mcriterion(as_nhwc(pr), as_label_index(gt), self.kind, self.class_w)
+
+
 class MDiceLoss(nn.Module):
+    """forward (reference miou.py:93-117): 1 - mean_{n,c} 2 (sum pg + 1e-6) / (sum p + sum g + 1e-6), sums over the pixels of one sample; bi=True adds the
+    same on the complements (1 - p, 1 - g)"""
+    class_w = None
+
+    def __init__(self, nb_class=2, bi=False):
+        super().__init__()
+        self.nb_class = nb_class        # accepted and unused, as in the reference: the class count is the logits'
+        self.bi = bool(bi)
+        self.kind = 'dice2' if self.bi else 'dice'
+
+    forward = _mforward
+
     @staticmethod
     def _per_class(pr, gt, smooth=1):
         c = _counts(pr, gt)
@@ -64,6 +86,16 @@ class MDiceLoss(nn.Module):
 
 
 class MIouLoss(nn.Module):
+    """forward (reference miou.py:46-62): 1 - mean_{n,c} sum pg / (sum p + sum g - sum pg + 1e-6), sums over the pixels of one sample"""
+    class_w = None
+    kind = 'iou'
+
+    def __init__(self, nb_class=4):
+        super().__init__()
+        self.nb_class = nb_class
+
+    forward = _mforward
+
     @staticmethod
     def scorem(pr, gt, start_idx=0, smooth=1):
         c = _counts(pr, gt)

@@ -5,7 +5,9 @@ Additions: `--los=di+reg+fpl` shorthand (BASELINE.json) == `--los=di --reg=true 
 GOALS-shaped generator; `--pl=true` = one process per GPU under torchrun; `--dtype=bf16|fp32` compute precision;
 `--los=d2|iou|mse` name the reference's other per-class criteria (DiceLoss(bi=True), IouLoss, nn.MSELoss; the reference's
 own `get_loss` only reaches Dice and MSE), also inside the shorthand (`--los=iou+reg+fpl`); `--los_weight=1,1,2,2,1` = the
-`weight` list of `MultiLoss` (per-class weights; the reference passes it in code only).
+`weight` list of `MultiLoss` (per-class weights; the reference passes it in code only); `--mlos=di|d2|iou|ce` selects the criterion
+through the reference's second factory, `kite/losses/lossm.py::get_mloss` (Dice / IoU per sample and per class, cross-entropy with
+`--los_weight` as its class weights), while `--los` keeps naming the auxiliary losses: `--mlos=ce --los=di+reg+fpl`.
 
     python -m tcct_amd.kite.main --bs=8 --net=stc_tt --los=di --db=synth --epochs=1
 """
@@ -63,6 +65,9 @@ def build_parser():
                         'six-map feats; --net=stc_tt / tcct only)')
     p.add_argument('--los_weight', type=float_list, default=[],
                    help='per-class weights of the criterion, comma-separated (MultiLoss(weight=...)); classes beyond the end of the list are dropped, as in the reference')
+    p.add_argument('--mlos', type=str, default='', choices=['', 'di', 'd2', 'iou', 'ce'],
+                   help="criterion from get_mloss (kite/losses/lossm.py) instead of get_loss(--los): 'di' / 'd2' = MDiceLoss(bi=False / True), 'iou' = MIouLoss "
+                        "(per sample and per class), 'ce' = nn.CrossEntropyLoss(weight=--los_weight); --los still names the +reg+fpl auxiliary losses")
     p.add_argument('--graph', type=str2bool, default=False,
                    help='EXPERIMENTAL: replay the training step from a hipGraph (launch-bound crop sizes such as the 256x256 of the reference '
                         'recipe; single process, fixed batch shape).  A capture late in a long process has crashed inside hipGraphLaunch '

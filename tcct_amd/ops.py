@@ -3346,6 +3346,133 @@ def deep_supervision_criterion(logits0_nhwc, labels, lows, coff, kind='dice', cl
     return _DeepSupervisionCrit.apply(logits0_nhwc, labels, float(coff), H, W, code, class_w, *[l_.low for l_ in lows])
 
 
+# The criteria of the reference's get_mloss (kite/losses/lossm.py over kite/losses/miou.py): Dice / dice2 / IoU taken per SAMPLE and per class, and
+# nn.CrossEntropyLoss(weight) -- tcct_softmax_mcrit_* / tcct_upmcrit_* / tcct_mcrit_ds_fwd (csrc/mcrit.hip).  sums fp64 [head][B][3][C].
+MCRIT_KINDS = {'dice': 0, 'dice2': 1, 'iou': 2, 'ce': 3}
+
+
+def _mcrit_args(kind, class_w, C, device):
+    """-> (kind code, class_w).  Only 'ce' takes class weights: the reference's MDiceLoss / MIouLoss have none."""
+    if kind not in MCRIT_KINDS:
+        raise TcctError(f'm-criterion kind {kind!r}: one of {sorted(MCRIT_KINDS)}')
+    if class_w is not None:
+        if kind != 'ce':
+            raise TcctError(f'm-criterion kind {kind!r} takes no class weights (only \'ce\' does)')
+        if not (torch.is_tensor(class_w) and class_w.dtype == torch.float32 and class_w.dim() == 1 and class_w.numel() >= C and class_w.is_contiguous()
+                and class_w.device == device):
+            raise TcctError(f'class weights: a contiguous fp32 vector of at least {C} entries on {device} is needed')
+    return MCRIT_KINDS[kind], class_w
+
+
+class _SoftmaxMCrit(_FastFunction):
+    @staticmethod
+    def forward(ctx, logits, labels, kind, class_w):
+        _chk(logits, labels)
+        B, C = logits.shape[0], logits.shape[-1]
+        HW = logits.numel() // (B * C)
+        sums = torch.empty(B * 3 * C, device=logits.device, dtype=torch.float64)
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        lib.softmax_mcrit_fwd(logits, labels, B, HW, C, kind, class_w, sums, loss, dtype_code(logits.dtype))
+        ctx.save_for_backward(logits, labels, sums)
+        ctx.cfg = (kind, class_w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, sums = ctx.saved_tensors
+        kind, class_w = ctx.cfg
+        B, C = logits.shape[0], logits.shape[-1]
+        HW = logits.numel() // (B * C)
+        g = _as(g, torch.float32)
+        d = torch.empty_like(logits)
+        lib.softmax_mcrit_bwd(logits, labels, B, HW, C, kind, class_w, sums, g, 1.0, d, dtype_code(logits.dtype))
+        return d, None, None, None
+
+
+class _UpMCrit(_FastFunction):
+    """<m-criterion>(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits"""
+
+    @staticmethod
+    def forward(ctx, low, labels, H, W, kind, class_w):
+        _chk(low, labels)
+        B, h, w, C = low.shape
+        sums = torch.empty(B * 3 * C, device=low.device, dtype=torch.float64)
+        loss = torch.empty((), device=low.device, dtype=torch.float32)
+        lib.upmcrit_fwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, loss)
+        ctx.save_for_backward(low, labels, sums)
+        ctx.cfg = (H, W, kind, class_w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, labels, sums = ctx.saved_tensors
+        B, h, w, C = low.shape
+        H, W, kind, class_w = ctx.cfg
+        g = _as(g, torch.float32)
+        ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
+        d = torch.empty_like(low)
+        lib.upmcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, g, 1.0, ws, d)
+        return d, None, None, None, None, None
+
+
+class _DeepSupervisionMCrit(_FastFunction):
+    """_DeepSupervisionCrit for the m-criteria: one memset, up to four sums kernels, one finalisation"""
+
+    @staticmethod
+    def forward(ctx, logits0, labels, coff, H, W, kind, class_w, *lows):
+        _chk(logits0, labels, *lows)
+        B, _, _, C = logits0.shape
+        sums = torch.empty(4 * B * 3 * C, device=logits0.device, dtype=torch.float64)
+        loss = torch.empty((), device=logits0.device, dtype=torch.float32)
+        a = []
+        for i in range(3):
+            a += [lows[i], lows[i].shape[1], lows[i].shape[2]] if i < len(lows) else [None, 0, 0]
+        lib.mcrit_ds_fwd(logits0, dtype_code(logits0.dtype), labels, B, H, W, C, *a, coff, kind, class_w, sums, loss)
+        ctx.save_for_backward(logits0, labels, sums, *lows)
+        ctx.cfg = (coff, H, W, kind, class_w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits0, labels, sums, *lows = ctx.saved_tensors
+        coff, H, W, kind, class_w = ctx.cfg
+        B, _, _, C = logits0.shape
+        per = B * 3 * C
+        g = _as(g, torch.float32)
+        d0 = torch.empty_like(logits0)
+        lib.softmax_mcrit_bwd(logits0, labels, B, H * W, C, kind, class_w, sums[:per], g, 1.0, d0, dtype_code(logits0.dtype))
+        dl = []
+        for i, low in enumerate(lows):
+            _, h, w, _ = low.shape
+            ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
+            d = torch.empty_like(low)
+            lib.upmcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums[(i + 1) * per:(i + 2) * per], g, coff, ws, d)
+            dl.append(d)
+        return (d0, None, None, None, None, None, None) + tuple(dl)
+
+
+def softmax_mcriterion(logits, labels, kind, class_w=None):
+    """MDiceLoss(bi=False / True), MIouLoss, nn.CrossEntropyLoss(weight): logits NHWC [N,H,W,C], labels uint8 [N,H,W] -> scalar.  kind: 'dice' | 'dice2' | 'iou' (per
+    sample and class, mean over N*C) | 'ce' (weighted mean over the pixels); class_w: fp32 device vector [>= C] or None, 'ce' only."""
+    code, class_w = _mcrit_args(kind, class_w, logits.shape[-1], logits.device)
+    return _SoftmaxMCrit.apply(logits, labels, code, class_w)
+
+
+def softmax_mcriterion_upsampled(lr, labels, kind, class_w=None):
+    """the m-criterion of a LowResLogits head"""
+    if not lr.fusable():
+        return softmax_mcriterion(bilinear(lr.low, lr.size, False), labels, kind, class_w)
+    code, class_w = _mcrit_args(kind, class_w, lr.low.shape[-1], lr.low.device)
+    return _UpMCrit.apply(lr.low, labels, lr.size[0], lr.size[1], code, class_w)
+
+
+def deep_supervision_mcriterion(logits0_nhwc, labels, lows, coff, kind, class_w=None):
+    """deep_supervision_criterion for the m-criteria (same gate: deep_supervision_dice_ok)"""
+    code, class_w = _mcrit_args(kind, class_w, logits0_nhwc.shape[-1], logits0_nhwc.device)
+    H, W = lows[0].size
+    return _DeepSupervisionMCrit.apply(logits0_nhwc, labels, float(coff), H, W, code, class_w, *[l_.low for l_ in lows])
+
+
 DS_DICE_FUSE = True        # False: one criterion node per head + torch scalar arithmetic (A/B timing)
 
 

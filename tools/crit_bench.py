@@ -1,6 +1,7 @@
 """The criterion family (dice / dice2 / iou / mse with class weights: tcct_softmax_crit_*, tcct_upcrit_*, tcct_crit_ds_fwd) at the bench shape (bs 8, 800 x 1104,
 5 classes; heads at 1/1, 1/2, 1/4, 1/8), kernel by kernel (HIP events), beside the Dice kernels of the same build (tools/dice_bench.py's calls).  Prints a markdown
-table: forward (memset + sums + finalisation) and backward of each head, and the fused four-head forward, with the ratio to the Dice entry points.
+table: forward (memset + sums + finalisation) and backward of each head, and the fused four-head forward, with the ratio to the Dice entry points.  The criteria of
+get_mloss (per-sample dice / dice2 / iou, cross-entropy: tcct_softmax_mcrit_*, tcct_upmcrit_*, tcct_mcrit_ds_fwd) follow as extra rows, same columns.
 
     python tools/crit_bench.py      (the table belongs into profiles/criteria_summary.md, section "Kernel times")"""
 import os
@@ -11,6 +12,7 @@ from tcct_amd._lib import lib
 from tools.kbench import timeit
 
 KINDS = (('dice', 0), ('dice2', 1), ('iou', 2), ('mse', 3))
+MKINDS = (('dice', 0), ('dice2', 1), ('iou', 2), ('ce', 3))
 
 
 def main():
@@ -63,6 +65,22 @@ def main():
                          lambda i: lib.upcrit_bwd(lows[i], lab, B, lows[i].shape[1], lows[i].shape[2], H, W, C, code, w_, sm(i), g, 0.5, wss[i], dls[i]),
                          lambda: lib.crit_ds_fwd(logits, 0, lab, B, H, W, C, *ds_args, 0.5, code, w_, sums, loss))
             rows.append((f'{name}{wn}', r, val))
+    per = B * 3 * C                 # the m-criteria keep sums per sample: [head][B][3][C]
+    msums = torch.zeros(4 * per, device=dev, dtype=torch.float64)
+
+    def msm(i):
+        return msums[(i + 1) * per:(i + 2) * per]
+
+    for name, code in MKINDS:
+        for w_, wn in ((None, ''), (cw, ' + weights')):
+            if w_ is not None and name != 'ce':
+                continue            # only cross-entropy takes class weights
+            r, val = row(lambda: lib.softmax_mcrit_fwd(logits, lab, B, H * W, C, code, w_, msums[:per], loss, 0),
+                         lambda: lib.softmax_mcrit_bwd(logits, lab, B, H * W, C, code, w_, msums[:per], g, 1.0, d0, 0),
+                         lambda i: lib.upmcrit_fwd(lows[i], lab, B, lows[i].shape[1], lows[i].shape[2], H, W, C, code, w_, msm(i), loss),
+                         lambda i: lib.upmcrit_bwd(lows[i], lab, B, lows[i].shape[1], lows[i].shape[2], H, W, C, code, w_, msm(i), g, 0.5, wss[i], dls[i]),
+                         lambda: lib.mcrit_ds_fwd(logits, 0, lab, B, H, W, C, *ds_args, 0.5, code, w_, msums, loss))
+            rows.append((f'get_mloss {name}{wn}', r, val))
     cols = ['head 0 fwd', 'head 0 bwd', '1/2 fwd', '1/2 bwd', '1/4 fwd', '1/4 bwd', '1/8 fwd', '1/8 bwd', 'fused 4-head fwd']
     print(f'{torch.cuda.get_device_name(0)}; bs {B}, {H} x {W}, C = {C}, fp32 logits; microseconds per call (HIP events, 20 calls after 3 warm-up calls; a forward is memset + sums')
     print('kernel + finalisation, an upsampled backward is its two passes), in brackets the ratio to the Dice entry point of the same build in the first row.')
