@@ -268,6 +268,19 @@ int64_t tcct_conv32_wgrad_mode(int mode);
 int64_t tcct_conv32_fwd_mode(int mode);
 int tcct_conv32_wgrad_strided(const void* x, const void* dy, float* dw, float* dbias, int N, int H, int W, int KH, int KW, int PH,
                               int PW, int xs, int xo, int ds, int dof, int cin_total, int o_off, int i_off, tcct_stream_t stream);
+/* The 32 -> 64 3x3 'same' convolution (MPViT stem[1], nets/tcct.py:682-689) as ONE launch of the wide row-stream kernels per direction instead of two slab launches:
+ * wave pairs walk one strip, one 32-channel output (dy) slab each, so x (and every 128-byte dy line) crosses HBM once.
+ * fwd33: y [N,H,W,64] = conv(x [N,H,W,32]) + bias[64] (nullable); wp = the forward packs of w[0:32] and w[32:64] (tcct_conv32_pack_weights layout), wps bf16 elements
+ * apart; stats (nullable) fp64 {sum[64], sum of squares[64]} of pre_act(y) as stored, zero on entry.  Bit-identical to tcct_conv32_fwd_strided(_bnstats) x 2.
+ * wgrad33: dw OIHW fp32 [64,32,3,3] and dbias [64] (nullable) ACCUMULATE (zero them first), as tcct_conv32_wgrad_strided.
+ * Maps below the row-stream thresholds (and tcct_conv32_fwd_mode / tcct_conv32_wgrad_mode 1) run the slab launches inside these calls; force != 0 (or mode 2) takes
+ * the wide kernels at any size. */
+int tcct_conv32x64_fwd33(const void* x, const void* wp, int wps, const float* bias, void* y, int N, int H, int W, double* stats, int pre_act, int force,
+                         tcct_stream_t stream);
+int tcct_conv32x64_wgrad33(const void* x, const void* dy, float* dw, float* dbias, int N, int H, int W, int force, tcct_stream_t stream);
+/* dgrad33: dx [N,H,W,32] from dy [N,H,W,64] in one launch: dy crosses HBM once, the 64-channel reduction stays in fp32 and dx is rounded to bf16 once (the slab
+ * path's second launch adds into a bf16 partial dx).  wp_t = the input-gradient packs of w[0:32], w[32:64] (second half of tcct_conv32_pack_weights_both), wps apart. */
+int tcct_conv64x32_dgrad33(const void* dy, const void* wp_t, int wps, void* dx, int N, int H, int W, int force, tcct_stream_t stream);
 /* weight/bias gradient of the same family (ds_read_b64_tr_b16 transposing LDS reads feed the pixel-contraction MFMA);
  * dw OIHW fp32 [32,32,KH,KW] and dbias fp32 [32] (nullable) are overwritten */
 int tcct_conv32_wgrad(const void* x, const void* dy, float* dw, float* dbias, int N, int H, int W, int KH, int KW, int PH,

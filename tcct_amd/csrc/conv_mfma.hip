@@ -437,7 +437,7 @@ k_conv32_mfma(const bf16* __restrict__ x, const bf16* __restrict__ wp, const flo
 /* x, y: bf16 NHWC [N,H,W,32]; wp: packed bf16 [KH*KW][32][32] from tcct_conv32_pack_weights; stride 1; output size == input
  * size requires PH = (KH-1)/2 etc. but any PH <= KH-1, PW <= KW-1 with "same" output extent H x W is accepted. */
 static bool conv32_fwd33_stream_launch(const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, double* stats, int stat_code, int stats_sq_off,
-                                       bool force, hipStream_t st, const float* aff = nullptr);
+                                       bool force, hipStream_t st, const float* aff = nullptr, int wps = 0);
 static bool conv32_fwd1k_stream_launch(const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int K, bool force, hipStream_t st);
 static bool conv32_fwdk1_stream_launch(const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int K, bool force, hipStream_t st);
 static int g_fwd_mode = -1;
@@ -960,12 +960,18 @@ k_conv32_wgrad33_roll(const bf16* __restrict__ x, const bf16* __restrict__ dy, f
 #define WS_ROWB 2176            // 18 x pixels (1152 B) + 16 dy pixels (1024 B)
 #define WS_MIN_RUN 32            // rows per wave below which the pipeline fill (7 rows per segment) costs more than the tiles' barriers: levels 0-1 stream, 2-4 roll
 // (lds_dma16 / make_rsrc_words: common.h)
+// WIDE (dW [64][32][3][3], MPViT stem[1]): the waves form PAIRS on one strip; wave 2 p + o takes the 64-byte half o of dy's 128-byte pixels (output channels 32 o ..+31) against
+// its own ring copy of the SAME x rows -- the pair's DMA addresses coincide in time, so every 128-byte dy line and every x line crosses HBM once, the second reader hits L2 --
+// and the closing reduction keeps one LDS image per slab (2 x 36 KB): still one global atomic per element and block.  dbias [64].
+template <bool WIDE>
 __global__ void __launch_bounds__(WS_T, 2)
 k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, float* __restrict__ dw, float* __restrict__ dbias,
                         int N, int H, int W, int strips, int run) {
+    constexpr int SL = WIDE ? 2 : 1, NS = WS_T / 64 / SL;        // dy slabs = waves per strip; strips per block
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
+    const int slab = WIDE ? (wave & 1) : 0, ws_ = WIDE ? (wave >> 1) : wave;
     unsigned char* ring = smem + wave * (WS_R * WS_ROWB);
     const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
     const unsigned char* xb = tr_lane_base(ring, lane);
@@ -976,7 +982,7 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
         for (int k = 0; k < 16; ++k) acc[t][k] = 0.f;
     float bsum = 0.f;
     // the four waves of a block walk four ADJACENT strips over the same rows (4 KB of every x / dy row between them at about the same time)
-    const int sgroups = (strips + 3) >> 2;
+    const int sgroups = (strips + NS - 1) / NS;
     const int64_t total = (int64_t)N * sgroups * H;
     int64_t cur = (int64_t)blockIdx.x * run;        // (a row-major block order -- the strip groups of one run of image rows on consecutive blocks -- pays for the
     const int64_t end = cur + run < total ? cur + run : total;      //  forward kernel below, not here: 0.176 ms either way)
@@ -985,17 +991,17 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
     const int px = lane >> 2, c = lane & 3;
     while (cur < end) {
         const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * 4 + wave;
+        const int n = sidx / sgroups, s = (sidx - n * sgroups) * NS + ws_;
         const int left = (int)(end - cur);
         const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // dy rows r0 .. r0 + L - 1; x rows r0 - 1 .. r0 + L
         if (s >= strips) { cur += L; continue; }
         const int w0 = s * 16;
         const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
-        const u32x4 rd = make_rsrc_words(dy + (int64_t)n * H * W * 32, img_bytes);
+        const u32x4 rd = make_rsrc_words(dy + (int64_t)n * H * W * (32 * SL), img_bytes * SL);
         const int cx1 = w0 - 1 + px, cx2 = w0 + 15 + px, cd = w0 + px;
         const uint32_t ox1 = (cx1 >= 0 && cx1 < W) ? (uint32_t)(cx1 * 64 + c * 16) : OOB_OFF;
         const uint32_t ox2 = (cx2 < W) ? (uint32_t)(cx2 * 64 + c * 16) : OOB_OFF;
-        const uint32_t od = (cd < W) ? (uint32_t)(cd * 64 + c * 16) : OOB_OFF;
+        const uint32_t od = (cd < W) ? (uint32_t)(cd * (64 * SL) + slab * 64 + c * 16) : OOB_OFF;
         const uint32_t row0 = (uint32_t)(r0 - 1) * rowb;            // r0 = 0: wraps far beyond the descriptor range -> zeros (the padding row)
         // halo row a of the segment -> ring slot `slot`; rows behind the segment (a > L + 1) and dy rows a >= L are all-miss pieces (zeros, no HBM traffic)
         auto issue = [&](int a, int slot) {
@@ -1004,7 +1010,7 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
             const uint32_t base = ring_lds + (uint32_t)(slot * WS_ROWB);
             lds_dma16(rx, xin ? ox1 + ro : OOB_OFF, base);
             if (lane < 8) lds_dma16(rx, xin ? ox2 + ro : OOB_OFF, base + 1024u);
-            lds_dma16(rd, din ? od + ro + rowb : OOB_OFF, base + 1152u);
+            lds_dma16(rd, din ? od + (ro + rowb) * SL : OOB_OFF, base + 1152u);
         };
 #pragma unroll
         for (int a = 0; a < WS_P; ++a) issue(a, a);
@@ -1042,33 +1048,35 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the all-miss pieces behind the segment: the next segment reuses their slots
         cur += L;
     }
-    // the four waves of a block take turns adding their nine 32 x 32 partial sums into one LDS image (no LDS float atomics), then one atomic per element
+    // the waves of a block take turns adding their nine 32 x 32 partial sums into one LDS image per dy slab (no LDS float atomics), then one atomic per element
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);
-    for (int turn = 0; turn < WS_T / 64; ++turn) {
-        if (wave == turn) {
+    for (int turn = 0; turn < NS; ++turn) {
+        if (ws_ == turn) {
 #pragma unroll
             for (int t = 0; t < 9; ++t)
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
                     const int co = (k & 3) + 8 * (k >> 2) + 4 * hh;
-                    float* dst = &red[t * 1024 + co * 32 + r];
+                    float* dst = &red[slab * 9216 + t * 1024 + co * 32 + r];
                     *dst = turn == 0 ? acc[t][k] : *dst + acc[t][k];
                 }
         }
         __syncthreads();
     }
-    for (int i = tid; i < 9 * 1024; i += WS_T) {
-        const int tap = i % 9, cc = i / 9;          // OIHW-linear order: 256 contiguous bytes per wave instruction
-        atomicAdd(&dw[(int64_t)cc * 9 + tap], red[tap * 1024 + cc]);
+    for (int i = tid; i < 9 * 1024 * SL; i += WS_T) {
+        const int o = WIDE ? i / 9216 : 0, e = i - o * 9216;
+        const int tap = e % 9, cc = e / 9;          // OIHW-linear order (output channel 32 o + cc / 32): 256 contiguous bytes per wave instruction
+        atomicAdd(&dw[i], red[o * 9216 + tap * 1024 + cc]);
     }
     __syncthreads();
     if (dbias) {
         bsum += __shfl_xor(bsum, 32, 64);
         if (lane < 32) red[wave * 32 + r] = bsum;
         __syncthreads();
-        if (tid < 32) atomicAdd(&dbias[tid], red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid]);
+        if (!WIDE && tid < 32) atomicAdd(&dbias[tid], red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid]);
+        if (WIDE && tid < 64) atomicAdd(&dbias[tid], red[tid] + red[64 + tid]);         // channel tid = 32 o + c: waves o and o + 2
     }
 }
 
@@ -1089,18 +1097,27 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
 #ifndef FS_SYNC
 #define FS_SYNC 1
 #endif
-template <int STATS>            // 0: none; 1: statistics of y; 2: of LeakyReLU(y) (y as stored) -> stats[0..31], stats[stats_sq_off ..+32) (fp64 atomics);
+template <int STATS, bool WIDE = false>            // 0: none; 1: statistics of y; 2: of LeakyReLU(y) (y as stored) -> stats[0..31], stats[stats_sq_off ..+32) (fp64 atomics);
                                 // 4 / 5 / 6: inference epilogue y = post(a[c] * pre(conv + bias) + b[c]) (eval-mode BatchNorm folded in, as k_conv32_mfma<.., 4, ..>) with
                                 // (pre, post) = (none, none) / (none, LeakyReLU) / (LeakyReLU, none) -- compile-time: the run-time switch of affine4(), unrolled 9 x 4
                                 // times, made an 18 000-line kernel with scratch that ran SLOWER than the tiled one
+                                // WIDE (32 -> 64, MPViT stem[1]): the waves of a block form PAIRS on one strip, wave 2 p + o computes output slab o (channels 32 o ..+31: pack
+                                // wp + o wps, bias + 32 o) of strip p from its own ring of the SAME x rows -- the pair issues the same DMA addresses at the same time, so the
+                                // second fetch is an L2 hit -- and stores the 64-byte half o of y's 128-byte pixels; statistics {sum[64], sum of squares[64]}.  Per output
+                                // channel the arithmetic is the plain kernel's: bit-identical to two slab launches of the tiled kernel.
 __global__ void __launch_bounds__(FS_T, 2)      // two waves per SIMD: <= 256 VGPRs
 k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, const float* __restrict__ bias, bf16* __restrict__ y,
                       int N, int H, int W, int strips, int run, int rpi, double* __restrict__ stats, int stats_sq_off,
-                      const float* __restrict__ aff) {
+                      const float* __restrict__ aff, int wps) {
+    static_assert(!(WIDE && STATS >= 4), "k_conv32_fwd33_stream: the wide form has no inference epilogue");
+    constexpr int SL = WIDE ? 2 : 1, NB = 32 * SL;          // output slabs = waves per strip; bias floats in front of the statistics partials
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int nw = blockDim.x >> 6;             // waves = adjacent strips per block (4)
+    const int nw = blockDim.x >> 6;             // waves per block (4)
+    const int ns = nw / SL;                     // adjacent strips per block
+    const int slab = WIDE ? (wave & 1) : 0, ws_ = WIDE ? (wave >> 1) : wave;         // output slab and strip-in-block of this wave
+    if (WIDE) wp += slab * wps;
     unsigned char* ring = smem + wave * (FS_R * FS_ROWB);
     const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
     float* sB = reinterpret_cast<float*>(smem + nw * FS_R * FS_ROWB);          // bias[32], then the statistics partials [nw][64]
@@ -1109,7 +1126,8 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) Wf[t][kc] = *reinterpret_cast<const bf16x8*>(wp + (t * 32 + r) * 32 + (hh + 2 * kc) * 8);
-    if (tid < 32) sB[tid] = bias ? bias[tid] : 0.f;
+    if (tid < NB) sB[tid] = bias ? bias[tid] : 0.f;
+    const float* sBl = sB + 32 * slab;          // this wave's 32 biases
     if (STATS >= 4 && tid < 64) sB[32 + tid] = aff ? aff[tid] : (tid < 32 ? 1.f : 0.f);     // a[32], b[32] of the folded BatchNorm (the statistics partials' place)
     __syncthreads();
     const unsigned char* xB[3][2];
@@ -1122,7 +1140,7 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
 #pragma unroll
     for (int k = 0; k < (ST ? 8 : 1); ++k) ss[k] = sq[k] = 0.f;
     // the waves of a block walk ADJACENT strips over the same rows (nw x 2 KB of every image row between them, at about the same time)
-    const int sgroups = (strips + nw - 1) / nw;
+    const int sgroups = (strips + ns - 1) / ns;
     // Row-major block order: consecutive blocks take the strip groups of ONE run of image rows, so whole image rows are in flight together (0.1838 ms at
     // level 0 against 0.1893 for runs cut from the strip-major sequence of rows).  rpi = runs per image; a block has one run of one strip group.
     int64_t cur, end;
@@ -1138,7 +1156,7 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
     const int p16 = lane >> 2, cch = lane & 3;
     while (cur < end) {
         const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * nw + wave;
+        const int n = sidx / sgroups, s = (sidx - n * sgroups) * ns + ws_;
         const int left = (int)(end - cur);
         const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // output rows r0 .. r0 + L - 1; halo rows r0 - 1 .. r0 + L
         if (s >= strips) {
@@ -1149,14 +1167,14 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
         }
         const int w0 = s * 32;
         const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
-        const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * NB), 0, img_bytes * SL, 0x00020000);
         const int c0 = w0 - 1 + pq, c1 = w0 + 15 + pq, c2 = w0 + 31 + pq;
         const uint32_t o0 = (c0 >= 0 && c0 < W) ? (uint32_t)(c0 * 64 + cs * 16) : OOB_OFF;
         const uint32_t o1 = (c1 < W) ? (uint32_t)(c1 * 64 + cs * 16) : OOB_OFF;
         const uint32_t o2 = (c2 < W) ? (uint32_t)(c2 * 64 + cs * 16) : OOB_OFF;
         uint32_t so[2];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) { const int wo = w0 + 16 * u + p16; so[u] = wo < W ? (uint32_t)(wo * 64 + cch * 16) : OOB_OFF; }
+        for (int u = 0; u < 2; ++u) { const int wo = w0 + 16 * u + p16; so[u] = wo < W ? (uint32_t)(wo * (64 * SL) + slab * 64 + cch * 16) : OOB_OFF; }
         const uint32_t row0 = (uint32_t)(r0 - 1) * rowb;
         auto issue = [&](int a, int slot) {
             const uint32_t ro = row0 + (uint32_t)a * rowb;
@@ -1195,7 +1213,7 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
                 {           // output row a starts at the bias of this lane's 16 channels
                     float4 bq[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const float4*>(sB + 8 * q + 4 * hh);
+                    for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const float4*>(sBl + 8 * q + 4 * hh);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { acc[j % 3][4 * q] = bq[q].x; acc[j % 3][4 * q + 1] = bq[q].y; acc[j % 3][4 * q + 2] = bq[q].z; acc[j % 3][4 * q + 3] = bq[q].w; }
                 }
@@ -1233,7 +1251,7 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
 #pragma unroll
                 for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(sc + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
                 wave_lds_fence();
-                const uint32_t oro = (uint32_t)(r0 + orow) * rowb;
+                const uint32_t oro = (uint32_t)(r0 + orow) * (rowb * SL);
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const bool inb = ovalid && so[u] != OOB_OFF;
@@ -1264,7 +1282,7 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
         // a lane owns channels 8 (lane & 3) ..+7 of the pixels it stored: butterfly over lane bits 2..5, per-wave LDS slots, fp64 atomics (as k_conv32_mfma)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        float* red = sB + 32;
+        float* red = sB + NB;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             float a = ss[k], b = sq[k];
@@ -1276,19 +1294,21 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
             }
         }
         __syncthreads();
-        if (tid < 64) {
+        if (tid < 64 * SL) {
+            const int o = tid >> 6, c = tid & 63;           // output slab o: the waves o, o + SL, ...
             double t = 0.0;
-            for (int w = 0; w < nw; ++w) t += (double)red[w * 64 + tid];
-            atomicAdd(&stats[tid < 32 ? tid : stats_sq_off + tid - 32], t);
+            for (int w = o; w < nw; w += SL) t += (double)red[w * 64 + c];
+            atomicAdd(&stats[(c < 32 ? c : stats_sq_off + c - 32) + 32 * o], t);
         }
     }
 }
 /* plain 32-channel 3x3 (no slabs, no accumulate, STATS 0-2): true when the row-stream kernel was launched */
 static bool conv32_fwd33_stream_launch(const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, double* stats, int stat_code, int stats_sq_off,
-                                       bool force, hipStream_t st, const float* aff) {
+                                       bool force, hipStream_t st, const float* aff, int wps) {
+    const bool wide = wps > 0;          // 32 -> 64: wave pairs, two strips per block (stat_code 0-2 only)
     const int strips = (W + 31) / 32;
     const int nw = 4;           // 4 waves x 2 blocks per CU (7 or 8 waves in one block per CU: 0.197 ms against 0.190 at level 0)
-    const int sg = (strips + nw - 1) / nw;
+    const int sg = (strips + (wide ? 2 : nw) - 1) / (wide ? 2 : nw);
     // runs per image: as many as fill the 512 block slots, each at least FS_MIN_RUN rows long (the pipeline fill is FS_P rows per run)
     int rpi = 512 / (N * sg);
     if (rpi > H / FS_MIN_RUN) rpi = H / FS_MIN_RUN;
@@ -1297,11 +1317,24 @@ static bool conv32_fwd33_stream_launch(const void* x, const void* wp, const floa
     rpi = (H + run - 1) / run;
     const int blocks = N * rpi * sg;
     if (!force && (H < FS_MIN_RUN || blocks < 384)) return false;       // small maps: the tiled kernel
-    const size_t lds = (size_t)nw * FS_R * FS_ROWB + 128 + (size_t)nw * 256;
+    const size_t lds = (size_t)nw * FS_R * FS_ROWB + (wide ? 256 : 128) + (size_t)nw * 256;
+#define FS_LAUNCH(S, WD)                                                                                                                                      \
+    do {                                                                                                                                                      \
+        tcct_launch<k_conv32_fwd33_stream<S, WD>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, \
+                           run, rpi, stats, stats_sq_off, aff, wps);                                                                                             \
+    } while (0)
+    if (wide) {
+        if (stat_code == 0) FS_LAUNCH(0, true);
+        else if (stat_code == 1) FS_LAUNCH(1, true);
+        else FS_LAUNCH(2, true);
+        tcct_census_hit(TCCT_CENSUS_FWD33_STREAM);
+        return true;
+    }
+#undef FS_LAUNCH
 #define FS_LAUNCH(S)                                                                                                                                          \
     do {                                                                                                                                                      \
         tcct_launch<k_conv32_fwd33_stream<S>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, \
-                           run, rpi, stats, stats_sq_off, aff);                                                                                                  \
+                           run, rpi, stats, stats_sq_off, aff, 0);                                                                                               \
     } while (0)
     if (stat_code == 0) FS_LAUNCH(0);
     else if (stat_code == 1) FS_LAUNCH(1);
@@ -1310,6 +1343,167 @@ static bool conv32_fwd33_stream_launch(const void* x, const void* wp, const floa
     else if (stat_code == 5) FS_LAUNCH(5);
     else FS_LAUNCH(6);
 #undef FS_LAUNCH
+    tcct_census_hit(TCCT_CENSUS_FWD33_STREAM);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ 3x3 input gradient 64 -> 32 (MPViT stem[1]), one launch
+// k_conv32_fwd33_stream with TWO input slabs per pixel: dy has 64 channels (128-byte pixels, read from HBM once), the K = 64 reduction of an output row stays in its fp32
+// accumulator and dx is rounded to bf16 once (the slab path's second launch re-read and re-rounded a bf16 partial dx).  Budgets: 36 weight fragments (144 VGPRs) + 2 x 12 B
+// fragments (96) + 3 rolling accumulators (48) do not fit beside a second wave on the SIMD, and a halo row is 34 x 128 B = 4352 B, so nine ring rows x four waves are
+// 153 KB: ONE block of four waves per CU, one wave per SIMD with the 512-register budget, everything in registers as in the 32 -> 32 kernel (no weight image in LDS, no
+// block barrier beyond the pacing one).  Seven rows x 4352 B x 4 waves = 119 KB are in flight per CU -- more than the 2 x 4 x 7 x 2176 B of the 32 -> 32 kernel.
+// Ring image: chunk c (16 B = 8 channels, 0-7) of ring pixel P sits at position c ^ ((P >> 1) & 7) of its 128-byte row: the sixteen pixels of a ds_read_b128 lane group
+// hit sixteen distinct 16-byte bank slots at dx = 0, 1, 2.  A halo row is five DMA pieces of 8 pixels (the last one 2 pixels): `s_waitcnt vmcnt(5 (DG_P - 1))`, stores not
+// counted (see k_conv32_fwd33_stream).
+#define DG_R 9
+#define DG_P 7
+#define DG_ROWB 4352            // 34 halo pixels x 128 B
+__global__ void __launch_bounds__(FS_T, 1)      // one wave per SIMD: <= 512 VGPRs
+k_conv64x32_dgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, int wps, bf16* __restrict__ y, int N, int H, int W, int strips, int run, int rpi) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, hh = lane >> 5;
+    const int nw = blockDim.x >> 6;             // waves = adjacent strips per block (4)
+    unsigned char* ring = smem + wave * (DG_R * DG_ROWB);
+    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
+    bf16x8 Wf[2][9][2];         // A operands: input slab sl, row co = r, input channels 32 sl + 8 hh + 16 half ..+7 of tap t
+#pragma unroll
+    for (int sl = 0; sl < 2; ++sl)
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int kc = 0; kc < 2; ++kc) Wf[sl][t][kc] = *reinterpret_cast<const bf16x8*>(wp + (size_t)sl * wps + (t * 32 + r) * 32 + (hh + 2 * kc) * 8);
+    const unsigned char* xB[3][4];          // [dx][2 sl + half]
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const int P = r + d; xB[d][c] = ring + P * 128 + (((hh + 2 * c) ^ ((P >> 1) & 7)) << 4); }
+    const int sgroups = (strips + nw - 1) / nw;
+    int64_t cur, end;
+    {
+        const int q = blockIdx.x / sgroups, grp = blockIdx.x - q * sgroups;
+        const int n_ = q / rpi, r_ = (q - n_ * rpi) * run;
+        cur = ((int64_t)n_ * sgroups + grp) * H + r_;
+        end = cur + (H - r_ < run ? H - r_ : run);
+    }
+    const uint32_t ximg = (uint32_t)H * (uint32_t)W * 128u, yimg = (uint32_t)H * (uint32_t)W * 64u;
+    const uint32_t xrowb = (uint32_t)W * 128u, yrowb = (uint32_t)W * 64u;
+    const int p8 = lane >> 3;               // DMA piece k: ring pixel 8 k + p8, LDS position lane & 7 holds chunk (lane & 7) ^ ((4 k + (lane >> 4)) & 7)
+    const int p16 = lane >> 2, cch = lane & 3;
+    while (cur < end) {
+        const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
+        const int n = sidx / sgroups, s = (sidx - n * sgroups) * nw + wave;
+        const int left = (int)(end - cur);
+        const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // output rows r0 .. r0 + L - 1; halo rows r0 - 1 .. r0 + L
+        if (s >= strips) {
+#if FS_SYNC
+            for (int g = 0; g < (L + 2 + DG_R - 1) / DG_R; ++g) __builtin_amdgcn_s_barrier();
+#endif
+            cur += L; continue;
+        }
+        const int w0 = s * 32;
+        const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 64, ximg);
+        const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, yimg, 0x00020000);
+        uint32_t po[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int col = w0 - 1 + 8 * k + p8, cs = (lane & 7) ^ ((4 * k + (lane >> 4)) & 7);
+            po[k] = (col >= 0 && col < W) ? (uint32_t)(col * 128 + cs * 16) : OOB_OFF;
+        }
+        uint32_t so[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) { const int wo = w0 + 16 * u + p16; so[u] = wo < W ? (uint32_t)(wo * 64 + cch * 16) : OOB_OFF; }
+        const uint32_t row0 = (uint32_t)(r0 - 1) * xrowb;
+        auto issue = [&](int a, int slot) {
+            const uint32_t ro = row0 + (uint32_t)a * xrowb;
+            const bool xin = a <= L + 1;
+            const uint32_t base = ring_lds + (uint32_t)(slot * DG_ROWB);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lds_dma16(rx, xin ? po[k] + ro : OOB_OFF, base + 1024u * k);
+            if (lane < 16) lds_dma16(rx, xin ? po[4] + ro : OOB_OFF, base + 4096u);
+        };
+#pragma unroll
+        for (int a = 0; a < DG_P; ++a) issue(a, a);
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(5 * (DG_P - 1)) : "memory");
+        bf16x8 X[3][4], Xn[3][4];
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) X[d][c] = *reinterpret_cast<const bf16x8*>(xB[d][c]);
+        f32x16 acc[3];
+        const int groups = (L + 2 + DG_R - 1) / DG_R;
+        for (int g = 0; g < groups; ++g) {
+#if FS_SYNC
+            __builtin_amdgcn_s_barrier();           // keeps the four strips of a block on the same rows (no data is shared)
+#endif
+#pragma unroll
+            for (int j = 0; j < DG_R; ++j) {
+                const int a = g * DG_R + j;
+                issue(a + DG_P, (j + DG_P) % DG_R);
+                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(5 * (DG_P - 1)) : "memory");         // halo row a + 1 has landed (stores not counted)
+#pragma unroll
+                for (int d = 0; d < 3; ++d)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) Xn[d][c] = *reinterpret_cast<const bf16x8*>(xB[d][c] + ((j + 1) % DG_R) * DG_ROWB);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) acc[j % 3][k] = 0.f;          // output row a starts (an input gradient has no bias)
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy)          // halo row a is tap row dy of output row a - dy
+#pragma unroll
+                    for (int d = 0; d < 3; ++d)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c)
+                            acc[(j + 3 - dy) % 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[c >> 1][dy * 3 + d][c & 1], X[d][c], acc[(j + 3 - dy) % 3], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                // output row a - 2 is complete: pack, transpose through the free ring slot (the one halo row a + 8 will land in), two 1 KB stores
+                const int orow = a - 2;
+                const bool ovalid = orow >= 0 && orow < L;
+                const f32x16& A = acc[(j + 1) % 3];
+                unsigned char* sc = ring + ((j + 8) % DG_R) * DG_ROWB;
+                uint2 o[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { o[q].x = pack_bf16x2(A[4 * q], A[4 * q + 1]); o[q].y = pack_bf16x2(A[4 * q + 2], A[4 * q + 3]); }
+                const int f = (r >> 1) & 3;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(sc + r * 64 + ((q ^ f) << 4) + hh * 8) = o[q];
+                wave_lds_fence();
+                u32x4 pend[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(sc + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
+                wave_lds_fence();
+                const uint32_t oro = (uint32_t)(r0 + orow) * yrowb;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const bool inb = ovalid && so[u] != OOB_OFF;
+                    __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, inb ? so[u] + oro : OOB_OFF, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int d = 0; d < 3; ++d)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) X[d][c] = Xn[d][c];
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        cur += L;
+    }
+}
+/* true when the row-stream kernel was launched (maps whose waves get >= FS_MIN_RUN rows and that fill most CUs, or force) */
+static bool conv64x32_dgrad33_stream_launch(const void* dy, const void* wp, int wps, void* dx, int N, int H, int W, bool force, hipStream_t st) {
+    const int strips = (W + 31) / 32;
+    const int nw = 4;
+    const int sg = (strips + nw - 1) / nw;
+    int rpi = 256 / (N * sg);           // one block per CU
+    if (rpi > H / FS_MIN_RUN) rpi = H / FS_MIN_RUN;
+    if (rpi < 1) rpi = 1;
+    const int run = (H + rpi - 1) / rpi;
+    rpi = (H + run - 1) / run;
+    const int blocks = N * rpi * sg;
+    if (!force && (H < FS_MIN_RUN || blocks < 192)) return false;
+    const size_t lds = (size_t)nw * DG_R * DG_ROWB;
+    tcct_launch<k_conv64x32_dgrad33_stream, 160 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)dy, (const bf16*)wp, wps, (bf16*)dx, N, H, W, strips, run, rpi);
     tcct_census_hit(TCCT_CENSUS_FWD33_STREAM);
     return true;
 }
@@ -2035,7 +2229,7 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
             if (run < 12) run = 12;                 // small maps: fewer, longer runs (the pipeline fill is 7 rows)
             blocks = (int)((rows + run - 1) / run);
             constexpr size_t ldss = (size_t)(WS_T / 64) * WS_R * WS_ROWB;
-            tcct_launch<k_conv32_wgrad33_stream, 80 * 1024>(dim3((unsigned)blocks), dim3(WS_T), ldss, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run);
+            tcct_launch<k_conv32_wgrad33_stream<false>, 80 * 1024>(dim3((unsigned)blocks), dim3(WS_T), ldss, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run);
             tcct_census_hit(TCCT_CENSUS_WGRAD33_STREAM);
             TCCT_LAUNCH_OK();
         }
@@ -2099,6 +2293,74 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
     else { if (vert) WG_LAUNCH(5, true, false); else WG_LAUNCH(5, false, false); }
 #undef WG_LAUNCH
     TCCT_LAUNCH_OK();
+}
+
+// ------------------------------------------------------------------------------------------------ 32 -> 64 3x3 (MPViT stem[1]): one launch per direction
+/* y [N,H,W,64] = conv3x3(x [N,H,W,32]) + bias[64] in ONE launch of the wide row-stream kernel (x crosses HBM once); wp = the two forward packs of the output slabs
+ * w[0:32], w[32:64] (each as tcct_conv32_pack_weights makes it), wps bf16 elements apart.  stats (nullable): fp64 {sum[64], sum of squares[64]} of pre_act(y) as
+ * stored, zero on entry.  Bit-identical to the two tcct_conv32_fwd_strided(_bnstats) launches, which small maps (the row-stream thresholds of tcct_conv32_fwd_mode,
+ * mode 1) and other pre-activations still take unless `force`. */
+extern "C" int tcct_conv32x64_fwd33(const void* x, const void* wp, int wps, const float* bias, void* y, int N, int H, int W, double* stats, int pre_act, int force,
+                                    tcct_stream_t stream) {
+    TCCT_CHECK(wps >= 9 * 1024 && wps % 8 == 0, "conv32x64_fwd33: bad pack distance %d", wps);
+    TCCT_CHECK(N > 0 && H > 0 && W > 0 && (int64_t)H * W * 128 < (1LL << 31), "conv32x64_fwd33: one image of %d x %d x 64 channels exceeds the 2 GiB buffer-descriptor range", H, W);
+    if (g_fwd_mode < 0) (void)tcct_conv32_fwd_mode(-1);
+    const bool has_code = !stats || pre_act == TCCT_ACT_NONE || pre_act == TCCT_ACT_LRELU;
+    if ((force || g_fwd_mode != 1) && has_code) {
+        if (conv32_fwd33_stream_launch(x, wp, bias, y, N, H, W, stats, !stats ? 0 : (pre_act == TCCT_ACT_NONE ? 1 : 2), 64, force || g_fwd_mode == 2, (hipStream_t)stream, nullptr, wps))
+            TCCT_LAUNCH_OK();
+    }
+    for (int o = 0; o < 2; ++o) {
+        const int rc = conv32_fwd_impl(x, (const bf16*)wp + (size_t)o * wps, bias ? bias + 32 * o : nullptr, y, N, H, W, 3, 3, 1, 1, 32, 0, 64, 32 * o, 0,
+                                       stats ? stats + 32 * o : nullptr, pre_act, stream, nullptr, 0, false, nullptr, 64);
+        if (rc) return rc;
+    }
+    return 0;
+}
+/* dx [N,H,W,32] = the input gradient of the same convolution from dy [N,H,W,64] in ONE launch (dy crosses HBM once, the 64-channel reduction stays in fp32, one bf16
+ * rounding); wp_t = the input-gradient (flipped / transposed) packs of w[0:32] and w[32:64] (the second half of tcct_conv32_pack_weights_both), wps bf16 elements apart.
+ * Small maps / tcct_conv32_fwd_mode 1 take the two accumulating tcct_conv32_fwd_strided launches unless `force`. */
+extern "C" int tcct_conv64x32_dgrad33(const void* dy, const void* wp_t, int wps, void* dx, int N, int H, int W, int force, tcct_stream_t stream) {
+    TCCT_CHECK(wps >= 9 * 1024 && wps % 8 == 0, "conv64x32_dgrad33: bad pack distance %d", wps);
+    TCCT_CHECK(N > 0 && H > 0 && W > 0 && (int64_t)H * W * 128 < (1LL << 31), "conv64x32_dgrad33: one image of %d x %d x 64 channels exceeds the 2 GiB buffer-descriptor range", H, W);
+    if (g_fwd_mode < 0) (void)tcct_conv32_fwd_mode(-1);
+    if (force || g_fwd_mode != 1) {
+        if (conv64x32_dgrad33_stream_launch(dy, wp_t, wps, dx, N, H, W, force || g_fwd_mode == 2, (hipStream_t)stream)) TCCT_LAUNCH_OK();
+    }
+    for (int i = 0; i < 2; ++i) {
+        const int rc = conv32_fwd_impl(dy, (const bf16*)wp_t + (size_t)i * wps, nullptr, dx, N, H, W, 3, 3, 1, 1, 64, 32 * i, 32, 0, i, nullptr, 0, stream);
+        if (rc) return rc;
+    }
+    return 0;
+}
+/* dw OIHW fp32 [64,32,3,3] += dy [N,H,W,64] (x) x [N,H,W,32], dbias [64] (nullable) += sum dy, in ONE launch of the wide row-stream kernel (every dy and x line crosses HBM
+ * once).  ACCUMULATES like tcct_conv32_wgrad_strided: zero dw / dbias first.  Maps below the row-stream threshold of tcct_conv32_wgrad_mode (and mode 1) take the two
+ * strided launches unless `force`. */
+extern "C" int tcct_conv32x64_wgrad33(const void* x, const void* dy, float* dw, float* dbias, int N, int H, int W, int force, tcct_stream_t stream) {
+    TCCT_CHECK(N > 0 && H > 0 && W > 0 && (int64_t)H * W * 128 < (1LL << 31), "conv32x64_wgrad33: one image of %d x %d x 64 channels exceeds the 2 GiB buffer-descriptor range", H, W);
+    if (g_wgrad_mode < 0) (void)tcct_conv32_wgrad_mode(-1);
+    const int m33 = g_wgrad_mode >= 3 ? 0 : g_wgrad_mode;
+    if (force || m33 != 1) {
+        const int strips = (W + 15) / 16;
+        const int64_t rows = (int64_t)N * ((strips + 1) / 2) * H;            // rows of strip groups (two adjacent strips, one wave pair each)
+        int blocks = 512;
+        int64_t run = (rows + blocks - 1) / blocks;
+        if (force || m33 == 2 || run >= WS_MIN_RUN) {
+            if (run < 12) run = 12;
+            blocks = (int)((rows + run - 1) / run);
+            constexpr size_t ldss = (size_t)(WS_T / 64) * WS_R * WS_ROWB;
+            static_assert(ldss >= 2 * 9 * 4096, "k_conv32_wgrad33_stream<true>: the two reduction images live in the rings");
+            tcct_launch<k_conv32_wgrad33_stream<true>, 80 * 1024>(dim3((unsigned)blocks), dim3(WS_T), ldss, (hipStream_t)stream, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W,
+                                                                  strips, (int)run);
+            tcct_census_hit(TCCT_CENSUS_WGRAD33_STREAM);
+            TCCT_LAUNCH_OK();
+        }
+    }
+    for (int o = 0; o < 2; ++o) {
+        const int rc = conv32_wgrad_impl(x, dy, dw, dbias, N, H, W, 3, 3, 1, 1, 32, 0, 64, 32 * o, 32, 32 * o, 0, 0, stream);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ fused backward (3x3)

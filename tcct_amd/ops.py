@@ -65,7 +65,8 @@ ZERO = _ZeroPool()
 # next step on begin_step() re-packs ALL of them with one launch (the optimizer has just changed the weights) and the forward pass picks its
 # pack out of the cache.  `PACK_ALL = False` (bench.py --set PACK_ALL=0) restores the per-call launches.
 PACK_ALL = True
-# ent: id(weight) -> [weakref(weight), pack buffer, (KH, KW), data_ptr, step last looked up].  Entries hold NO strong reference to the weight:
+# ent: key -> [weakref(weight), pack buffer, (KH, KW, byte offset of the packed rows in the weight), data_ptr, step last looked up]; key = id(weight), or
+# (id(weight), o) for the 32-output slab o of the 32 -> 64 stem convolution (_pack_lookup_wide).  Entries hold NO strong reference to the weight:
 # a dead model's entries disappear at the next begin_step(), as do entries no convolution asked for during the previous step.
 # frozen / keep: once a hipGraph has captured a step whose pack launch reads a descriptor table, that table and the pack buffers it names are kept
 # alive for the life of the process (`keep`) -- a replay reads their addresses -- and a changed entry set builds a NEW table beside them.
@@ -84,9 +85,9 @@ def _pack_lookup(w, KH, KW):
     if not (PACK_ALL and ZERO.active):
         return None
     ent = _PACKS['ent'].get(id(w))
-    if ent is None or ent[0]() is not w or ent[3] != w.data_ptr() or ent[2] != (KH, KW):
+    if ent is None or ent[0]() is not w or ent[3] != w.data_ptr() or ent[2] != (KH, KW, 0):
         wp2 = torch.empty(2 * KH * KW * 1024, device=w.device, dtype=torch.bfloat16)
-        _PACKS['ent'][id(w)] = [weakref.ref(w), wp2, (KH, KW), w.data_ptr(), _PACKS['step']]
+        _PACKS['ent'][id(w)] = [weakref.ref(w), wp2, (KH, KW, 0), w.data_ptr(), _PACKS['step']]
         _PACKS['sig'] = None                    # the descriptor table is rebuilt at the next begin_step()
         return None
     ent[4] = _PACKS['step']
@@ -94,6 +95,27 @@ def _pack_lookup(w, KH, KW):
         return None
     n = KH * KW * 1024
     return ent[1][:n], ent[1][n:]
+
+
+def _pack_lookup_wide(w):
+    """the 3x3 32 -> 64 weight (MPViT stem[1]) in the same registry: rows 32 o ..+31 of an OIHW [64, 32, 3, 3] weight are a contiguous [32, 32, 3, 3] weight of
+    their own, so each output slab is one more record of the pack-all launch.  -> one buffer [slab o][forward pack, input-gradient pack][9 * 1024] made by this
+    step's launch, or None"""
+    if not (PACK_ALL and ZERO.active):
+        return None
+    n = 9 * 1024
+    ents = [_PACKS['ent'].get((id(w), o)) for o in range(2)]
+    if any(e is None or e[0]() is not w or e[3] != w.data_ptr() for e in ents) or ents[1][1].data_ptr() != ents[0][1].data_ptr() + 4 * n:
+        buf = torch.empty(4 * n, device=w.device, dtype=torch.bfloat16)
+        for o in range(2):
+            _PACKS['ent'][(id(w), o)] = [weakref.ref(w), buf[2 * n * o:2 * n * (o + 1)], (3, 3, o * 32 * 32 * 9 * 4), w.data_ptr(), _PACKS['step']]
+        _PACKS['sig'] = None
+        return None
+    for e in ents:
+        e[4] = _PACKS['step']
+    if not _PACKS['fresh'] or _PACKS['sig'] is None or not (ents[0][5:] and ents[1][5:]):
+        return None
+    return ents[0][1]._base
 
 
 def _pack_evict():
@@ -110,11 +132,11 @@ def _pack_all(device):
     _PACKS['fresh'] = False
     if not (PACK_ALL and ents):
         return
-    sig = tuple((e[3], e[1].data_ptr()) for e in ents)
+    sig = tuple((e[3] + e[2][2], e[1].data_ptr()) for e in ents)
     if sig != _PACKS['sig'] and torch.cuda.is_current_stream_capturing():
         return                      # the descriptor upload is a host-to-device copy: not inside a hipGraph capture (the convolutions pack per call then)
     if sig != _PACKS['sig']:
-        rows = [[e[3], e[1].data_ptr(), e[2][0], e[2][1]] for e in ents]
+        rows = [[e[3] + e[2][2], e[1].data_ptr(), e[2][0], e[2][1]] for e in ents]
         _PACKS['desc'] = torch.tensor(rows, dtype=torch.int64).to(device)       # a NEW tensor: tables named by captured graphs stay in `keep`
         _PACKS['sig'] = sig
     for e in _PACKS['ent'].values():
@@ -361,6 +383,27 @@ def _mfma_slabs_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
             and (KH == 1 or KW == 1 or (KH == 3 and KW == 3)))
 
 
+# The 3x3 32 -> 64 convolution (MPViT stem[1], reference nets/tcct.py:682-689) as ONE launch per direction (tcct_conv32x64_fwd33 / tcct_conv64x32_dgrad33 /
+# tcct_conv32x64_wgrad33: wave pairs per strip, x / dy read from HBM once, dx rounded once) with its packs out of the one-launch-per-step registry.  The forward is
+# bit-identical to the slab path; TCCT_WIDE_CONV=0 restores the slab path (A/B timing).
+WIDE_CONV = os.environ.get('TCCT_WIDE_CONV', '1') != '0'
+
+
+def _wide33_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
+    return (WIDE_CONV and in_dt == torch.bfloat16 and out_dt == torch.bfloat16 and Cin == 32 and Cin_w == 32 and Cout == 64 and KH == 3 and KW == 3
+            and stride == 1 and padh == 1 and padw == 1)
+
+
+def _wide_packs(w):
+    """[slab o][forward pack, input-gradient pack][9 * 1024] bf16 of an OIHW [64, 32, 3, 3] weight: this step's pack-all launch, else one launch per slab"""
+    buf = _pack_lookup_wide(w)
+    if buf is None:
+        buf = torch.empty(4 * 9 * 1024, device=w.device, dtype=torch.bfloat16)
+        for o in range(2):
+            lib.conv32_pack_weights_both(w[32 * o:], buf[2 * 9 * 1024 * o:], 3, 3)
+    return buf
+
+
 def _mfma_slabs_f32_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
     """wider fp32 stride-1 'same' convolutions as 32x32 sub-GEMMs of the fp32 MFMA kernels (MPViT stem[1] 32->64 is a third of the parity mode's
     convolution time on the VALU kernel; the wide CNN encoder of stc_tb / gtc_tb)"""
@@ -443,6 +486,13 @@ class _Conv2d(_FastFunction):
                 stats_box[1] = sums
             else:
                 lib.pw_fwd(x, w, bias, y, N * H * W, Cin, Cout, 0, dtype_code(odt))
+        elif _wide33_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
+            sums = None
+            if stats_box is not None:       # fused train-mode BN statistics of the consumer
+                sums = ZERO.get((2 * Cout,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * Cout, device=x.device, dtype=torch.float64)
+                stats_box[1] = sums
+            ctx.wp_wide = _wide_packs(w)
+            lib.conv32x64_fwd33(x, ctx.wp_wide, 2 * 9 * 1024, bias, y, N, H, W, sums, stats_box[0] if stats_box is not None else 0, 0)
         elif _mfma_slabs_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
             sums = None
             if stats_box is not None:       # fused train-mode BN statistics of the consumer (MPViT stem[1])
@@ -529,6 +579,11 @@ class _Conv2d(_FastFunction):
                     dskip = None
                 else:
                     lib.pw_fwd(dy, w, None, dx, N * H * W, Cout, Cin, 1, dtype_code(x.dtype))
+            elif _wide33_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
+                buf = getattr(ctx, 'wp_wide', None)
+                if buf is None:
+                    buf = _wide_packs(w)
+                lib.conv64x32_dgrad33(dy, buf[9 * 1024:], 2 * 9 * 1024, dx, N, H, W, 0)          # (a second consumer's gradient: the explicit pass below)
             elif _mfma_slabs_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw):
                 _conv_slabs_fwd(dy, w, None, dx, N, H, W, Cout, Cin, KH, KW, KH - 1 - padh, KW - 1 - padw, True)
             elif _mfma32_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw):
@@ -577,6 +632,12 @@ class _Conv2d(_FastFunction):
                                                       Cin, 32 * oh, 32 * ih)
                 elif F32_PW[2] and _pwf_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw) and Cout <= 160:
                     lib.pwf_wgrad(x, dy, dw, db, N * H * W, Cin, Cout)
+                elif _wide33_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
+                    if not ZERO.active:
+                        dw.zero_()
+                        if db is not None:
+                            db.zero_()
+                    lib.conv32x64_wgrad33(x, dy, dw, db, N, H, W, 0)
                 elif _mfma_slabs_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
                     if not ZERO.active:
                         dw.zero_()
