@@ -52,7 +52,7 @@ int tcct_u8_gather2d(const uint8_t* src, uint8_t* dst, int N, int SH, int SW, in
 int tcct_onehot_to_index(const int64_t* onehot, uint8_t* lab, int N, int C, int64_t HW, tcct_stream_t stream);
 /* int64 [N,H,Wsrc] class labels -> uint8 [N,H,Wdst] (columns >= Wsrc get class 0) */
 int tcct_labels_to_u8(const int64_t* lab, uint8_t* out, int N, int H, int Wsrc, int Wdst, tcct_stream_t stream);
-/* NHWC [M,C] -> NCHW-contiguous fp32 copy and back (API-boundary materialisation only) */
+/* NHWC [N,HW,C] -> NCHW-contiguous fp32 copy [N,C,HW] (API-boundary materialisation only); C <= 255 (a 64-pixel fp32 tile in 64 KB of LDS) */
 int tcct_nhwc_to_nchw_f32(const void* x, float* y, int N, int64_t HW, int C, int dtype, tcct_stream_t stream);
 
 /* ---- elementwise: nn.LeakyReLU / nn.Hardswish / nn.GELU / F.gelu / abs / sigmoid and residual adds
@@ -725,7 +725,8 @@ int tcct_hydra_apply_bwd(const void* qkv, const float* kv, const float* dkv, con
 
 /* ---- clip_grad_norm_(12) + AdamW on flat fp32 buffers (kite/loop_seg.py:128-130, kite/loopback.py:127) ------ */
 int tcct_grad_sumsq(const float* g, int64_t n, double* acc, tcct_stream_t stream);
-/* grad_mul pre-scales the raw gradient (1/world_size after a sum all-reduce); total_norm_out nullable */
+/* grad_mul pre-scales the raw gradient (1/world_size after a sum all-reduce); total_norm_out nullable.  1 - beta and the bias corrections are formed
+ * in double from the double betas; a NaN total norm gives a NaN clip coefficient (torch's clamp keeps NaN): every parameter is NaN after such a step */
 int tcct_clip_adamw(float* p, const float* g, float* m, float* v, int64_t n, const double* sumsq, float max_norm,
                     float grad_mul, float lr, double beta1, double beta2, float eps, float weight_decay, int step,
                     float* total_norm_out, tcct_stream_t stream);

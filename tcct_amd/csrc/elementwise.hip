@@ -157,7 +157,8 @@ __global__ void k_nhwc_to_nchw(const T* __restrict__ x, float* __restrict__ y, i
     }
 }
 extern "C" int tcct_nhwc_to_nchw_f32(const void* x, float* y, int N, int64_t HW, int C, int dtype, tcct_stream_t stream) {
-    TCCT_CHECK(C > 0 && C <= 512, "nhwc_to_nchw: bad C %d", C);
+    // the [64][C+1] fp32 tile goes through a plain launch, which carries 64 KB of dynamic LDS: 64 * (C + 1) * 4 <= 65536 up to C = 255
+    TCCT_CHECK(C > 0 && C <= 255, "nhwc_to_nchw: C=%d unsupported (1..255: the 64-pixel tile must fit 64 KB of LDS)", C);
     dim3 grid((unsigned)((HW + 63) / 64), N);
     size_t lds = (size_t)64 * (C + 1) * sizeof(float);
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_nhwc_to_nchw<T>, grid, dim3(256), lds, (hipStream_t)stream,

@@ -83,19 +83,27 @@ extern "C" int tcct_grad_sumsq(const float* g, int64_t n, double* acc, tcct_stre
     TCCT_LAUNCH_OK();
 }
 
+// torch.nn.utils.clip_grad_norm_: coef = clamp(max_norm / (total + 1e-6), max=1); gmul pre-scales the raw gradient (1/world).  A NaN norm (one NaN
+// gradient element) stays NaN, as torch's clamp keeps it: the step then turns every parameter NaN instead of quietly training on with the poisoned
+// elements alone (fminf returns its other operand for a NaN, i.e. "no clipping").
+__device__ __forceinline__ float clip_coef(float max_norm, float total) {
+    const float c = max_norm / (total + 1e-6f);
+    return c > 1.f ? 1.f : c;
+}
 __global__ void k_clip_adamw(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             int64_t n, const double* __restrict__ sumsq, float max_norm, float gmul, float lr, float b1, float b2,
+                             int64_t n, const double* __restrict__ sumsq, float max_norm, float gmul, float lr, double beta1, double beta2,
                              float eps, float wd, float bc1, float bc2, float* __restrict__ total_norm_out) {
-    // torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (total + 1e-6)); gmul pre-scales the raw gradient (1/world)
     const float total = sqrtf((float)(*sumsq)) * gmul;
-    const float coef = fminf(max_norm / (total + 1e-6f), 1.f) * gmul;
+    const float coef = clip_coef(max_norm, total) * gmul;
     if (total_norm_out && blockIdx.x == 0 && threadIdx.x == 0) *total_norm_out = total;
+    // the betas arrive as doubles: 1 - beta formed from the fp32 beta is 9.99987e-4 for beta2 = 0.999, 1.3e-5 off in v and 6e-6 in the update
+    const float b1 = (float)beta1, b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
     const float step = lr / bc1, isq2 = 1.f / sqrtf(bc2);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float gi = g[i] * coef;
         float pi = p[i] * (1.f - lr * wd);
-        float mi = b1 * m[i] + (1.f - b1) * gi;
-        float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        float mi = b1 * m[i] + omb1 * gi;
+        float vi = b2 * v[i] + omb2 * gi * gi;
         m[i] = mi; v[i] = vi;
         p[i] = pi - step * mi / (sqrtf(vi) * isq2 + eps);
     }
@@ -106,18 +114,21 @@ __global__ void k_clip_adamw(float* __restrict__ p, const float* __restrict__ g,
 // update reads the same value.
 __global__ void k_clip_adamw_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                  int64_t n, const double* __restrict__ sumsq, float max_norm, float gmul, const float* __restrict__ state,
-                                 float b1, float b2, float eps, float wd, float* __restrict__ total_norm_out) {
-    const float lr = state[0], t = state[1] + 1.f;
-    const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
+                                 double beta1, double beta2, float eps, float wd, float* __restrict__ total_norm_out) {
+    const float lr = state[0];
+    // bias corrections in double, as the host forms them for k_clip_adamw: 1 - powf(fp32 beta2, t) is 0.002 +- 3e-8 at t = 2, 1.5e-5 off
+    const double t = (double)state[1] + 1.0;
+    const float bc1 = (float)(1.0 - pow(beta1, t)), bc2 = (float)(1.0 - pow(beta2, t));
     const float total = sqrtf((float)(*sumsq)) * gmul;
-    const float coef = fminf(max_norm / (total + 1e-6f), 1.f) * gmul;
+    const float coef = clip_coef(max_norm, total) * gmul;
     if (total_norm_out && blockIdx.x == 0 && threadIdx.x == 0) *total_norm_out = total;
+    const float b1 = (float)beta1, b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
     const float step = lr / bc1, isq2 = 1.f / sqrtf(bc2);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         float gi = g[i] * coef;
         float pi = p[i] * (1.f - lr * wd);
-        float mi = b1 * m[i] + (1.f - b1) * gi;
-        float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        float mi = b1 * m[i] + omb1 * gi;
+        float vi = b2 * v[i] + omb2 * gi * gi;
         m[i] = mi; v[i] = vi;
         p[i] = pi - step * mi / (sqrtf(vi) * isq2 + eps);
     }
@@ -128,7 +139,7 @@ extern "C" int tcct_clip_adamw_dev(float* p, const float* g, float* m, float* v,
                                    float* total_norm_out, tcct_stream_t stream) {
     TCCT_CHECK(state != nullptr, "clip_adamw_dev: state is NULL");
     hipLaunchKernelGGL(k_clip_adamw_dev, dim3(tcct_grid(n, FB, 2048)), dim3(FB), 0, (hipStream_t)stream, p, g, m, v, n, sumsq, max_norm,
-                       grad_mul, state, (float)beta1, (float)beta2, eps, weight_decay, total_norm_out);
+                       grad_mul, state, beta1, beta2, eps, weight_decay, total_norm_out);
     hipLaunchKernelGGL(k_step_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, state);
     TCCT_LAUNCH_OK();
 }
@@ -138,6 +149,6 @@ extern "C" int tcct_clip_adamw(float* p, const float* g, float* m, float* v, int
     TCCT_CHECK(step >= 1, "clip_adamw: step must be >= 1");
     float bc1 = (float)(1.0 - pow(beta1, (double)step)), bc2 = (float)(1.0 - pow(beta2, (double)step));
     hipLaunchKernelGGL(k_clip_adamw, dim3(tcct_grid(n, FB, 2048)), dim3(FB), 0, (hipStream_t)stream, p, g, m, v, n, sumsq, max_norm,
-                       grad_mul, lr, (float)beta1, (float)beta2, eps, weight_decay, bc1, bc2, total_norm_out);
+                       grad_mul, lr, beta1, beta2, eps, weight_decay, bc1, bc2, total_norm_out);
     TCCT_LAUNCH_OK();
 }
