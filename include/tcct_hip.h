@@ -737,6 +737,23 @@ int tcct_clip_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n,
                         float grad_mul, float* state, double beta1, double beta2, float eps, float weight_decay,
                         float* total_norm_out, tcct_stream_t stream);
 
+/* ---- training batches from device-resident uint8 B-scans: the ALB_TWIST recipe of data/octgen.py:9-18 (PadIfNeeded, CropNonEmptyMaskIfExists,
+ * HorizontalFlip, VerticalFlip, RGBShift, HueSaturationValue, RandomContrast, RandomBrightness) + the ToTensor lines data/octgen.py:124-126.
+ * No RNG inside: the uniform draws are an input.  DESIGN 6 lists the formulas (the arithmetic is this project's own specification,
+ * restated in tests/augment_ref.py; bit parity with cv2 / albumentations is not claimed). */
+/* once at load (the np.argwhere(mask) of CropNonEmptyMaskIfExists, data/octgen.py:12, as a table): lab uint8 [N,SH,SW] -> cnt int32 [N,SH+1],
+ * cnt[n][y] = number of non-zero label pixels in rows < y; cnt[n][SH] = the image's total.  SH * SW < 2^31. */
+int tcct_aug_rowcount(const uint8_t* lab, int* cnt, int N, int SH, int SW, tcct_stream_t stream);
+/* once per batch (the draws of data/octgen.py:11-16 turned into parameters): u fp32 [B,16] uniform [0,1) draws, idx int32 [B] sample numbers
+ * (clamped to [0,N)) -> plan [B,16] 32-bit words: 0 sample, 1 y_min, 2 x_min (corner of the h x w crop in the padded PH x PW image), 3 flipx, 4 flipy,
+ * 5..7 r,g,b shift, 8 hue, 9 sat, 10 val shift, 11 contrast alpha, 12 brightness beta (5..12: fp32 bit patterns), 13 pad_top, 14 pad_left, 15 zero. */
+int tcct_aug_plan(const float* u, const int* idx, const int* cnt, const uint8_t* lab, int* plan, int B, int N, int SH, int SW, int h, int w,
+                  tcct_stream_t stream);
+/* hot path (the transforms of data/octgen.py:117-118 and the ToTensor lines 124-126): img uint8 [N,SH,SW,C] (C 1 or 3; 1 is replicated), lab uint8 [N,SH,SW],
+ * plan [B,16] -> out_img fp32 [B,3,h,w] in [0,1], out_lab uint8 [B,h,w].  Source positions outside the image read 0 (image and label). */
+int tcct_aug_apply(const uint8_t* img, const uint8_t* lab, const int* plan, float* out_img, uint8_t* out_lab, int B, int N, int SH, int SW, int C,
+                   int h, int w, tcct_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 `RegNet(net, con=args.type_udh, out_channels=...)`, `KiteSeg(...).fit(epochs)`.
 
 Additions: `--los=di+reg+fpl` shorthand (BASELINE.json) == `--los=di --reg=true --udh=true`; `--db=synth` synthetic
-GOALS-shaped generator; `--pl=true` = one process per GPU under torchrun; `--dtype=bf16|fp32` compute precision;
+GOALS-shaped generator; `--db=npz:FILE --crop=256,256` stored B-scans (tools/pack_dataset.py) cropped and augmented on the device; `--pl=true` = one process per GPU under torchrun; `--dtype=bf16|fp32` compute precision;
 `--los=d2|iou|mse` name the reference's other per-class criteria (DiceLoss(bi=True), IouLoss, nn.MSELoss; the reference's
 own `get_loss` only reaches Dice and MSE), also inside the shorthand (`--los=iou+reg+fpl`); `--los_weight=1,1,2,2,1` = the
 `weight` list of `MultiLoss` (per-class weights; the reference passes it in code only); `--mlos=di|d2|iou|ce` selects the criterion
@@ -29,6 +29,16 @@ def float_list(v):
         return [float(q) for q in v.split(',') if q.strip() != '']
     except ValueError:
         raise argparse.ArgumentTypeError(f'comma-separated floats expected, got {v!r}')
+
+
+def int_pair(v):
+    try:
+        h, w = (int(q) for q in v.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'H,W expected, got {v!r}')
+    if h < 16 or w < 16 or h % 16 or w % 16:
+        raise argparse.ArgumentTypeError(f'--crop={v}: H and W must be positive multiples of 16')
+    return (h, w)
 
 
 def build_parser():
@@ -72,6 +82,8 @@ def build_parser():
                    help='EXPERIMENTAL: replay the training step from a hipGraph (launch-bound crop sizes such as the 256x256 of the reference '
                         'recipe; single process, fixed batch shape).  A capture late in a long process has crashed inside hipGraphLaunch '
                         '(DESIGN 5b, cause open): use it from a fresh process only')
+    p.add_argument('--crop', type=int_pair, default=(256, 256),
+                   help='H,W of the training crops of --db=npz:FILE (the make_tran(256,256) of the reference, data/octgen.py:8-19); multiples of 16')
     return p
 
 
@@ -97,7 +109,7 @@ def main(argv=None):
     from .. import nets
     from ..data import EyeSetGenerator
     from .loop_seg import KiteSeg
-    dataset = EyeSetGenerator(dbname=args.db)
+    dataset = EyeSetGenerator(dbname=args.db, **(dict(crop=args.crop) if args.db.startswith('npz:') else {}))
     factory = getattr(nets, args.net, None)
     if factory is None:
         raise SystemExit(f'--net={args.net}: unknown network (available: stc_tt / tcct, stc_tb, gtc_tt, gtc_tb, cnnu, pnnu, vitu)')
