@@ -1,5 +1,6 @@
 // The criterion family of MultiLoss (reference kite/losses/loss.py:9-110) beside the Dice kernels of loss_classes.inc: softmax over C, per-class loss on batch-global
 // sums, classes added up with per-class weights.  Compiled three times by crit.hip (MAXC = 5 / 8 / 16, as loss.hip does).  NOT a stand-alone translation unit.
+// This file holds the family's own arithmetic (crit_accum, crit_grad_coeffs, crit_pixel_grad, the finalisation) and its kernels' outer loops; the shared pieces are loss_device.inc's.
 //   kind   slot 0 (A)         slot 1 (P)    slot 2 (G)    per-class loss
 //   dice   sum p g            sum p         sum g         1 - (1 + 2A) / (1 + P + G)
 //   dice2  sum p g            sum p^2       sum g         1 - (1 + 2A) / (1 + P + G)                (DiceLoss(bi=True): union = sum p^2 + sum g^2, g^2 = g)
@@ -25,27 +26,6 @@ __device__ __forceinline__ void crit_accum(const float (&p)[MAXC], int l, float 
         }
     }
 }
-// block tail of the sums kernels: wave sums -> LDS -> one fp64 atomic per (slot, class) and block (<= 512 blocks: the atomics serialise per address)
-template <int NB>
-__device__ __forceinline__ void crit_block_tail(const float (&A)[MAXC], const float (&P)[MAXC], const float (&G)[MAXC], int C, double* __restrict__ sums) {
-    __shared__ float sm[3 * MAXC][NB / 64];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        float a = wave_sum(A[c]), b = wave_sum(P[c]), g = wave_sum(G[c]);
-        if (lane == 0) { sm[c][w] = a; sm[MAXC + c][w] = b; sm[2 * MAXC + c][w] = g; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 * MAXC) {
-        int q = threadIdx.x / MAXC, c = threadIdx.x % MAXC;
-        if (c < C) {
-            double a = 0.0;
-            for (int k = 0; k < NB / 64; ++k) a += (double)sm[threadIdx.x][k];
-            atomicAdd(&sums[q * C + c], a);
-        }
-    }
-}
-
 #define CSB 1024
 template <typename T, int KIND>
 __global__ void __launch_bounds__(CSB) k_crit_sums(const T* __restrict__ logits, const uint8_t* __restrict__ lab, int64_t M, int C, double* __restrict__ sums /*[3][C]*/) {
@@ -59,7 +39,7 @@ __global__ void __launch_bounds__(CSB) k_crit_sums(const T* __restrict__ logits,
         softmax_inplace(z, C);
         crit_accum<KIND>(z, lab[i], A, P, G);
     }
-    crit_block_tail<CSB>(A, P, G, C, sums);
+    sums_block_tail<CSB>(A, P, G, C, sums);
 }
 template <int S, int KIND>
 __global__ void __launch_bounds__(UDB) k_upcrit_sums(const float* __restrict__ low, const uint8_t* __restrict__ lab, int B, int h, int w, int H, int W, int C, float sh,
@@ -67,7 +47,7 @@ __global__ void __launch_bounds__(UDB) k_upcrit_sums(const float* __restrict__ l
     float A[MAXC], P[MAXC], G[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) A[c] = P[c] = G[c] = 0.f;
-    // the item loop of k_updice_sums: a lane owns low-resolution column j of one full-resolution row, wave-uniform trip count (updice_rows exchanges columns between lanes)
+    // the item loop of k_updice_sums: items (row, j) flattened over the grid, wave-uniform trip count (updice_rows exchanges columns between lanes)
     const int items = B * H * w;
     const uint32_t m_w = w > 1 ? (uint32_t)((1ull << 32) / (uint32_t)w) : 0xffffffffu, m_H = H > 1 ? (uint32_t)((1ull << 32) / (uint32_t)H) : 0xffffffffu;
     for (int base = blockIdx.x * UDB + (threadIdx.x & ~63); base < items; base += gridDim.x * UDB) {
@@ -75,9 +55,8 @@ __global__ void __launch_bounds__(UDB) k_upcrit_sums(const float* __restrict__ l
         const int it = live ? base + (int)(threadIdx.x & 63) : items - 1;
         const int row = (int)udiv32(it, w, m_w), j = it - row * w;
         const int n = (int)udiv32(row, H, m_H), ho = row - n * H;
-        const Lerp a = src_index(ho, sh, h, 0);
         float R[3][MAXC];
-        updice_rows<S>(low, n, h, w, C, a, j, R, live);
+        updice_rows<S>(low, n, h, w, C, src_index(ho, sh, h, 0), j, R, live);
         if (!live) continue;
         const uint8_t* lr = lab + (int64_t)row * W + S * j;
 #pragma unroll
@@ -88,7 +67,7 @@ __global__ void __launch_bounds__(UDB) k_upcrit_sums(const float* __restrict__ l
             crit_accum<KIND>(z, lr[k], A, P, G);
         }
     }
-    crit_block_tail<UDB>(A, P, G, C, sums);
+    sums_block_tail<UDB>(A, P, G, C, sums);
 }
 
 __device__ __forceinline__ double crit_class_loss(int kind, const double* __restrict__ sm, int C, int c, double M) {
@@ -165,10 +144,9 @@ __global__ void k_crit_bwd(const T* __restrict__ logits, const uint8_t* __restri
             if (c < C) stf(dlogits + i * C + c, g[c]);
     }
 }
-// KEEP IN STEP with k_updice_bwd_w (loss_classes.inc): this is that kernel line for line, with crit_pixel_grad in place of the Dice gradient (the Dice kernel
-// stays as it is so that the benchmark's code does not change); an edit of the item loop, the halo lanes, the border clamps or the exchange belongs in both.
-// pass 1 of the upsampled backward: k_updice_bwd_w's scheme (every pixel evaluated once by the lane that owns its low-resolution column, the foreign tap's share travels
-// to the adjacent lane, 62 columns + 2 halo lanes per wave); pass 2 is k_updice_bwd_h itself
+// pass 1 of the upsampled backward: k_updice_bwd_w (loss_classes.inc, where the scheme is explained) with crit_pixel_grad as the gradient; pass 2 is k_updice_bwd_h itself.
+// The three pass-1 kernels stay three written-out loops: as shared helpers around the pixel loop, the body cost this kernel 1.3 % at the 1/8 head and took up to
+// 30 % more registers elsewhere (profiles/criterion_loops_summary.md).  A change of the halo lanes, the border clamps or the exchange is made in all three.
 template <int S>
 __global__ void __launch_bounds__(256) k_upcrit_bwd_w(const float* __restrict__ low, const uint8_t* __restrict__ lab, int B, int h, int w, int H, int W, int C, float sh,
                                                       int kind, const float* __restrict__ class_w, const double* __restrict__ sums, const float* __restrict__ gout,
@@ -239,10 +217,8 @@ static int crit_launch_sums(const void* logits, const uint8_t* labels, int64_t M
     return 0;
 }
 static int crit_launch_upsums(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, double* sums, hipStream_t st) {
-    const int Sc = h > 0 ? H / h : 0;
-    TCCT_CHECK(B >= 1 && h >= 1 && w >= 1 && H == Sc * h && W == Sc * w && (Sc == 2 || Sc == 4 || Sc == 8 || Sc == 16),
-               "upcrit: needs an integer scale 2/4/8/16 (got %dx%d -> %dx%d)", h, w, H, W);
-    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "upcrit: tensor too large");
+    int Sc;
+    if (int rc = upsampled_args_ok("upcrit", B, h, w, H, W, &Sc)) return rc;
     UPDICE_SCALES(Sc, CRIT_KINDS(kind, hipLaunchKernelGGL((k_upcrit_sums<S, KIND>), dim3(tcct_grid((int64_t)B * H * w, UDB, 512)), dim3(UDB), 0, st, low, labels, B, h, w, H, W, C,
                                                           (float)h / (float)H, sums)));
     return 0;
@@ -277,17 +253,13 @@ static int tcct_upcrit_fwd_impl(const float* low, const uint8_t* labels, int B, 
 static int tcct_upcrit_bwd_impl(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, const double* sums,
                                 const float* grad_out, float grad_scale, float* ws, float* dlow, tcct_stream_t stream) {
     CRIT_ARGS_OK("upcrit_bwd");
-    const int Sc = h > 0 ? H / h : 0;
-    TCCT_CHECK(B >= 1 && h >= 1 && w >= 1 && H == Sc * h && W == Sc * w && (Sc == 2 || Sc == 4 || Sc == 8 || Sc == 16),
-               "upcrit_bwd: needs an integer scale 2/4/8/16 (got %dx%d -> %dx%d)", h, w, H, W);
+    int Sc;
+    if (int rc = upsampled_args_ok("upcrit_bwd", B, h, w, H, W, &Sc)) return rc;
     TCCT_CHECK(ws != nullptr, "upcrit_bwd: workspace [B,H,w,C] fp32 is NULL");
-    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "upcrit_bwd: tensor too large");
     hipStream_t st = (hipStream_t)stream;
     UPDICE_SCALES(Sc, hipLaunchKernelGGL(k_upcrit_bwd_w<S>, dim3(tcct_grid((int64_t)B * H * ((w + 61) / 62), 4, 1 << 14)), dim3(256), 0, st, low, labels, B, h, w, H, W, C,
                                          (float)h / (float)H, kind, class_w, sums, grad_out, grad_scale, ws));
-    const int wC = w * C, gx2 = (wC + 255) / 256;
-    int gy2 = B * h; if (gy2 > 65535) gy2 = 65535;
-    hipLaunchKernelGGL(k_updice_bwd_h, dim3(gx2, gy2), dim3(256), 0, st, ws, B, h, wC, H, Sc, (float)h / (float)H, dlow);
+    launch_updice_bwd_h(ws, B, h, w, C, H, Sc, dlow, st);
     TCCT_LAUNCH_OK();
 }
 // the deep-supervision criterion as one launch sequence (tcct_dice_ds_fwd's layout): sums fp64 [(1 + nlow) * 3C], head 0 = the full-resolution one

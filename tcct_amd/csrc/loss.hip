@@ -21,17 +21,20 @@
 #include "loss_classes.inc"
 #undef MCNS
 
+#define DICE_BY_C(CALL) (C == 5 ? mc5::CALL : (C <= 8 ? mc8::CALL : mc16::CALL))
+#define PICK_BY_C(CALL) (C <= 8 ? mc8::CALL : mc16::CALL)        /* not on the training path: no 5-class instantiation of its own */
+
 extern "C" int tcct_softmax_dice_fwd(const void* logits, const uint8_t* labels, int64_t M, int C, double* sums, float* loss, int dtype, tcct_stream_t stream) {
-    return C == 5 ? mc5::tcct_softmax_dice_fwd_impl(logits, labels, M, C, sums, loss, dtype, stream) : (C <= 8 ? mc8::tcct_softmax_dice_fwd_impl(logits, labels, M, C, sums, loss, dtype, stream) : mc16::tcct_softmax_dice_fwd_impl(logits, labels, M, C, sums, loss, dtype, stream));
+    return DICE_BY_C(tcct_softmax_dice_fwd_impl(logits, labels, M, C, sums, loss, dtype, stream));
 }
 extern "C" int tcct_softmax_dice_bwd(const void* logits, const uint8_t* labels, int64_t M, int C, const double* sums, const float* grad_out, float grad_scale, void* dlogits, int dtype, tcct_stream_t stream) {
-    return C == 5 ? mc5::tcct_softmax_dice_bwd_impl(logits, labels, M, C, sums, grad_out, grad_scale, dlogits, dtype, stream) : (C <= 8 ? mc8::tcct_softmax_dice_bwd_impl(logits, labels, M, C, sums, grad_out, grad_scale, dlogits, dtype, stream) : mc16::tcct_softmax_dice_bwd_impl(logits, labels, M, C, sums, grad_out, grad_scale, dlogits, dtype, stream));
+    return DICE_BY_C(tcct_softmax_dice_bwd_impl(logits, labels, M, C, sums, grad_out, grad_scale, dlogits, dtype, stream));
 }
 extern "C" int tcct_updice_fwd(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, double* sums, float* loss, tcct_stream_t stream) {
-    return C == 5 ? mc5::tcct_updice_fwd_impl(low, labels, B, h, w, H, W, C, sums, loss, stream) : (C <= 8 ? mc8::tcct_updice_fwd_impl(low, labels, B, h, w, H, W, C, sums, loss, stream) : mc16::tcct_updice_fwd_impl(low, labels, B, h, w, H, W, C, sums, loss, stream));
+    return DICE_BY_C(tcct_updice_fwd_impl(low, labels, B, h, w, H, W, C, sums, loss, stream));
 }
 extern "C" int tcct_updice_bwd(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, const double* sums, const float* grad_out, float grad_scale, float* ws, float* dlow, tcct_stream_t stream) {
-    return C == 5 ? mc5::tcct_updice_bwd_impl(low, labels, B, h, w, H, W, C, sums, grad_out, grad_scale, ws, dlow, stream) : (C <= 8 ? mc8::tcct_updice_bwd_impl(low, labels, B, h, w, H, W, C, sums, grad_out, grad_scale, ws, dlow, stream) : mc16::tcct_updice_bwd_impl(low, labels, B, h, w, H, W, C, sums, grad_out, grad_scale, ws, dlow, stream));
+    return DICE_BY_C(tcct_updice_bwd_impl(low, labels, B, h, w, H, W, C, sums, grad_out, grad_scale, ws, dlow, stream));
 }
 /* KiteSeg.grad_calc with MultiLoss(DiceLoss) and deep supervision (reference kite/loopback.py:62-73, kite/losses/loss.py:15-32,83-99):
  *   loss = sum_{i = 3, 2, 1} coff * Dice(resize(low_i)) + Dice(logits)      (fp32 scalar arithmetic in that order)
@@ -43,13 +46,13 @@ extern "C" int tcct_dice_ds_fwd(const void* logits, int dtype, const uint8_t* la
     const float* lows[3] = {low1, low2, low3};
     const int lh[3] = {h1, h2, h3}, lw[3] = {w1, w2, w3};
     const int nlow = low1 ? (low2 ? (low3 ? 3 : 2) : 1) : 0;
-    return C == 5 ? mc5::tcct_dice_ds_fwd_impl(logits, dtype, labels, B, H, W, C, lows, lh, lw, nlow, coff, sums, loss, stream) : (C <= 8 ? mc8::tcct_dice_ds_fwd_impl(logits, dtype, labels, B, H, W, C, lows, lh, lw, nlow, coff, sums, loss, stream) : mc16::tcct_dice_ds_fwd_impl(logits, dtype, labels, B, H, W, C, lows, lh, lw, nlow, coff, sums, loss, stream));
+    return DICE_BY_C(tcct_dice_ds_fwd_impl(logits, dtype, labels, B, H, W, C, lows, lh, lw, nlow, coff, sums, loss, stream));
 }
 extern "C" int tcct_softmax_pick(const void* logits, const uint8_t* labels, int64_t M, int C, float* prob_lab, uint8_t* argmax, int dtype, tcct_stream_t stream) {
-    return C <= 8 ? mc8::tcct_softmax_pick_impl(logits, labels, M, C, prob_lab, argmax, dtype, stream) : mc16::tcct_softmax_pick_impl(logits, labels, M, C, prob_lab, argmax, dtype, stream);
+    return PICK_BY_C(tcct_softmax_pick_impl(logits, labels, M, C, prob_lab, argmax, dtype, stream));
 }
 extern "C" int tcct_confusion_counts(const uint8_t* pred, const uint8_t* labels, int N, int64_t HW, int C, float* out, tcct_stream_t stream) {
-    return C <= 8 ? mc8::tcct_confusion_counts_impl(pred, labels, N, HW, C, out, stream) : mc16::tcct_confusion_counts_impl(pred, labels, N, HW, C, out, stream);
+    return PICK_BY_C(tcct_confusion_counts_impl(pred, labels, N, HW, C, out, stream));
 }
 
 // ----------------------------------------------------------------------- channel slice  T [M,C] -> fp32 [M,n] and back

@@ -1,48 +1,35 @@
-// Class-count dependent loss kernels, compiled TWICE by loss.hip: MAXC = 8 (GOALS: 5 classes -- per-class arrays stay in few registers; the
-// VALU-bound resize+softmax+Dice kernels would pay for wider unrolled loops) and MAXC = 16 (the reference's 9-class Duke / HCMS models,
+// Class-count dependent loss kernels, compiled THREE times by loss.hip: MAXC = 5 (the benchmark's GOALS set has its own instantiation), MAXC = 8 (per-class arrays stay
+// in few registers; the VALU-bound resize+softmax+Dice kernels would pay for wider unrolled loops) and MAXC = 16 (the reference's 9-class Duke / HCMS models,
 // task1/onnx/tcct_duke.pt).  The C-ABI entry points in loss.hip pick the namespace by C.  NOT a stand-alone translation unit.
+// The Dice family of the three criterion families: its own arithmetic (dice_accum, dice_grad_coeffs, the finalisation) and its kernels' outer loops; the shared pieces are
+// loss_device.inc's.  k_dice_bwd keeps its softmax written out (see there).
 namespace MCNS {
+#include "loss_device.inc"      // softmax_inplace, sums_block_tail, udiv32, updice_rows, updice_pixel, UDB, UPDICE_SCALES, k_updice_bwd_h, ...
+// the Dice accumulation of one pixel: slots I = sum p g, P = sum p, G = sum g
+__device__ __forceinline__ void dice_accum(float (&z)[MAXC], int C, int l, float (&I)[MAXC], float (&P)[MAXC], float (&G)[MAXC]) {
+    softmax_inplace(z, C);
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        P[c] += z[c];
+        if (c == l) { I[c] += z[c]; G[c] += 1.f; }
+    }
+}
 // ----------------------------------------------------------------------- softmax + Dice sums (kite/losses/loss.py:28-32,83-99)
 // 1024-thread blocks on <= 512 blocks: the fp64 atomics at the end of every block serialise per address (see norm.hip)
 #define DSB 1024
 template <typename T>
 __global__ void __launch_bounds__(DSB) k_dice_sums(const T* __restrict__ logits, const uint8_t* __restrict__ lab, int64_t M, int C,
                             double* __restrict__ sums /*[3][C]: I, P, G*/) {
-    __shared__ float sm[3 * MAXC][DSB / 64];
     float I[MAXC], P[MAXC], G[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) I[c] = P[c] = G[c] = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (int64_t)gridDim.x * blockDim.x) {
-        float z[MAXC], mx = -INFINITY;
+        float z[MAXC];
 #pragma unroll
-        for (int c = 0; c < MAXC; ++c) { z[c] = c < C ? ldf(logits + i * C + c) : -INFINITY; mx = fmaxf(mx, z[c]); }
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) { z[c] = c < C ? __expf(z[c] - mx) : 0.f; s += z[c]; }
-        float inv = __builtin_amdgcn_rcpf(s);      // (v_rcp_f32, 1 ulp: the IEEE division is ten instructions per pixel)
-        int l = lab[i];
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            float p = z[c] * inv;
-            P[c] += p;
-            if (c == l) { I[c] += p; G[c] += 1.f; }
-        }
+        for (int c = 0; c < MAXC; ++c) z[c] = c < C ? ldf(logits + i * C + c) : -INFINITY;
+        dice_accum(z, C, lab[i], I, P, G);
     }
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        float a = wave_sum(I[c]), b = wave_sum(P[c]), g = wave_sum(G[c]);
-        if (lane == 0) { sm[c][w] = a; sm[MAXC + c][w] = b; sm[2 * MAXC + c][w] = g; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 * MAXC) {
-        int q = threadIdx.x / MAXC, c = threadIdx.x % MAXC;
-        if (c < C) {
-            double a = 0.0;
-            for (int k = 0; k < DSB / 64; ++k) a += (double)sm[threadIdx.x][k];
-            atomicAdd(&sums[q * C + c], a);
-        }
-    }
+    sums_block_tail<DSB>(I, P, G, C, sums);
 }
 __global__ void k_dice_finalize(const double* __restrict__ sums, int C, float* __restrict__ loss) {
     if (threadIdx.x == 0) {
@@ -85,6 +72,7 @@ __global__ void k_dice_bwd(const T* __restrict__ logits, const uint8_t* __restri
     const float gs = gscale * (gout ? *gout : 1.f);
     dice_grad_coeffs(sums, C, a, b);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (int64_t)gridDim.x * blockDim.x) {
+        // (softmax_inplace + the gradient, written out: through the helpers the 8-class instantiation needs one register more)
         float z[MAXC], mx = -INFINITY;
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) { z[c] = c < C ? ldf(logits + i * C + c) : -INFINITY; mx = fmaxf(mx, z[c]); }
@@ -113,22 +101,12 @@ static int tcct_softmax_dice_bwd_impl(const void* logits, const uint8_t* labels,
 // (F.interpolate bilinear, align_corners=False) and fed to the Dice criterion.  Materialised, each costs a 141 MB fp32 tensor written
 // and read in the forward and again (gradient) in the backward.  Here the interpolated logits are recomputed per pixel from the
 // low-resolution map (L2-resident), bit-identical to k_bilinear_fwd's arithmetic:
-//   forward : thread per full-resolution pixel -> softmax -> the three Dice sums;
-//   backward: dL/dlow = R_h^T R_w^T G with G the per-pixel softmax-Dice gradient: pass 1 evaluates G for the 2S pixels of a row that
-//             touch low-res column j and applies the column weights (T [B,H,w,C], <= 70 MB), pass 2 applies the row weights.
+//   forward : a lane per low-resolution column of a full-resolution row -> its S pixels -> softmax -> the three Dice sums;
+//   backward: dL/dlow = R_h^T R_w^T G with G the per-pixel softmax-Dice gradient: pass 1 applies the column weights (k_updice_bwd_w), pass 2 the row weights.
 // Integer scale S = H/h = W/w only (2, 4, 8 on the path).
-__device__ __forceinline__ void updice_logits(const float* __restrict__ r0, const float* __restrict__ r1, const Lerp& a, const Lerp& b,
-                                              int C, float (&z)[MAXC]) {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-        z[c] = c < C ? a.l0 * (b.l0 * r0[b.i0 * C + c] + b.l1 * r0[b.i1 * C + c]) + a.l1 * (b.l0 * r1[b.i0 * C + c] + b.l1 * r1[b.i1 * C + c])
-                     : -INFINITY;
-}
-#include "loss_device.inc"      // softmax_inplace, udiv32, updice_rows, updice_pixel, UDB, UPDICE_SCALES, k_updice_bwd_h
 template <int S>
 __global__ void __launch_bounds__(UDB) k_updice_sums(const float* __restrict__ low, const uint8_t* __restrict__ lab, int B, int h, int w,
                                                      int H, int W, int C, float sh, double* __restrict__ sums) {
-    __shared__ float sm[3 * MAXC][UDB / 64];
     float I[MAXC], P[MAXC], G[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) I[c] = P[c] = G[c] = 0.f;
@@ -141,50 +119,31 @@ __global__ void __launch_bounds__(UDB) k_updice_sums(const float* __restrict__ l
         const int it = live ? base + (int)(threadIdx.x & 63) : items - 1;
         const int row = (int)udiv32(it, w, m_w), j = it - row * w;
         const int n = (int)udiv32(row, H, m_H), ho = row - n * H;
-        const Lerp a = src_index(ho, sh, h, 0);
         float R[3][MAXC];
-        updice_rows<S>(low, n, h, w, C, a, j, R, live);
+        updice_rows<S>(low, n, h, w, C, src_index(ho, sh, h, 0), j, R, live);
         if (!live) continue;
         const uint8_t* lr = lab + (int64_t)row * W + S * j;
 #pragma unroll
         for (int k = 0; k < S; ++k) {
             float z[MAXC];
             updice_pixel<S>(R, k + S / 2, C, z);
-            softmax_inplace(z, C);
-            const int l = lr[k];
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                P[c] += z[c];
-                if (c == l) { I[c] += z[c]; G[c] += 1.f; }
-            }
+            dice_accum(z, C, lr[k], I, P, G);
         }
     }
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        float x = wave_sum(I[c]), y = wave_sum(P[c]), g = wave_sum(G[c]);
-        if (lane == 0) { sm[c][wv] = x; sm[MAXC + c][wv] = y; sm[2 * MAXC + c][wv] = g; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 * MAXC) {
-        const int q = threadIdx.x / MAXC, c = threadIdx.x % MAXC;
-        if (c < C) {
-            double t = 0.0;
-            for (int k = 0; k < UDB / 64; ++k) t += (double)sm[threadIdx.x][k];
-            atomicAdd(&sums[q * C + c], t);
-        }
-    }
+    sums_block_tail<UDB>(I, P, G, C, sums);
+}
+static int dice_launch_upsums(const char* what, const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, double* sums, hipStream_t st) {
+    int Sc;
+    if (int rc = upsampled_args_ok(what, B, h, w, H, W, &Sc)) return rc;
+    UPDICE_SCALES(Sc, hipLaunchKernelGGL(k_updice_sums<S>, dim3(tcct_grid((int64_t)B * H * w, UDB, 512)), dim3(UDB), 0, st, low, labels, B, h, w, H, W, C, (float)h / (float)H, sums));
+    return 0;
 }
 static int tcct_updice_fwd_impl(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, double* sums,
                                float* loss, tcct_stream_t stream) {
     TCCT_CHECK(C >= 2 && C <= MAXC, "updice_fwd: C=%d unsupported (2..%d)", C, MAXC);
-    const int Sc = h > 0 ? H / h : 0;
-    TCCT_CHECK(B >= 1 && h >= 1 && w >= 1 && H == Sc * h && W == Sc * w && (Sc == 2 || Sc == 4 || Sc == 8 || Sc == 16),
-               "updice_fwd: needs an integer scale 2/4/8/16 (got %dx%d -> %dx%d)", h, w, H, W);
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C, st) != hipSuccess) { tcct_set_error("updice_fwd: memset failed"); return -2; }
-    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "updice_fwd: tensor too large");
-    UPDICE_SCALES(Sc, hipLaunchKernelGGL(k_updice_sums<S>, dim3(tcct_grid((int64_t)B * H * w, UDB, 512)), dim3(UDB), 0, st, low, labels, B, h, w, H, W, C, (float)h / (float)H, sums));
+    if (int rc = dice_launch_upsums("updice_fwd", low, labels, B, h, w, H, W, C, sums, st)) return rc;
     hipLaunchKernelGGL(k_dice_finalize, dim3(1), dim3(64), 0, st, sums, C, loss);
     TCCT_LAUNCH_OK();
 }
@@ -196,7 +155,7 @@ static int tcct_updice_fwd_impl(const float* low, const uint8_t* labels, int B, 
 // Dice gradient twice, ~810 VALU instructions per item on the single-stream stretch behind the loss.  Waves tile a row with 62 columns each: lanes 0 and 63 are halo lanes
 // (they evaluate their pixels for the neighbours' sake, the adjacent wave writes their column).  Same per-pixel values; the three partial sums of a column are added as
 // (left + own) + right instead of pixel by pixel (fp32 reassociation, ~1e-7 relative).
-// (k_upcrit_bwd_w in crit_classes.inc is a copy of this kernel for the other criteria: KEEP THE TWO IN STEP)
+// k_upcrit_bwd_w (crit_classes.inc) and k_upmcrit_bwd_w (mcrit_classes.inc) are this loop with their own gradient, written out: see the note at k_upcrit_bwd_w.
 template <int S>
 __global__ void __launch_bounds__(256) k_updice_bwd_w(const float* __restrict__ low, const uint8_t* __restrict__ lab, int B, int h, int w,
                                                       int H, int W, int C, float sh, const double* __restrict__ sums,
@@ -262,18 +221,13 @@ __global__ void __launch_bounds__(256) k_updice_bwd_w(const float* __restrict__ 
 static int tcct_updice_bwd_impl(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, const double* sums,
                                const float* grad_out, float grad_scale, float* ws, float* dlow, tcct_stream_t stream) {
     TCCT_CHECK(C >= 2 && C <= MAXC, "updice_bwd: C=%d unsupported", C);
-    TCCT_CHECK(B >= 1 && h >= 1 && w >= 1 && H % h == 0 && W % w == 0 && H / h == W / w && H / h >= 2 && H / h <= 16,
-               "updice_bwd: needs an integer scale 2..16 (got %dx%d -> %dx%d)", h, w, H, W);
+    int Sc;
+    if (int rc = upsampled_args_ok("updice_bwd", B, h, w, H, W, &Sc)) return rc;
     TCCT_CHECK(ws != nullptr, "updice_bwd: workspace [B,H,w,C] fp32 is NULL");
     hipStream_t st = (hipStream_t)stream;
-    const int S = H / h;
-    TCCT_CHECK(S == 2 || S == 4 || S == 8 || S == 16, "updice_bwd: scale %d unsupported (2/4/8/16)", S);
-    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "updice_bwd: tensor too large");
-    { const int Sc = S; UPDICE_SCALES(Sc, hipLaunchKernelGGL(k_updice_bwd_w<S>, dim3(tcct_grid((int64_t)B * H * ((w + 61) / 62), 4, 1 << 14)), dim3(256), 0, st, low, labels, B, h, w, H, W, C, (float)h / (float)H,
-                                                              sums, grad_out, grad_scale, ws)); }
-    const int wC = w * C, gx2 = (wC + 255) / 256;
-    int gy2 = B * h; if (gy2 > 65535) gy2 = 65535;
-    hipLaunchKernelGGL(k_updice_bwd_h, dim3(gx2, gy2), dim3(256), 0, st, ws, B, h, wC, H, S, (float)h / (float)H, dlow);
+    UPDICE_SCALES(Sc, hipLaunchKernelGGL(k_updice_bwd_w<S>, dim3(tcct_grid((int64_t)B * H * ((w + 61) / 62), 4, 1 << 14)), dim3(256), 0, st, low, labels, B, h, w, H, W, C, (float)h / (float)H,
+                                         sums, grad_out, grad_scale, ws));
+    launch_updice_bwd_h(ws, B, h, w, C, H, Sc, dlow, st);
     TCCT_LAUNCH_OK();
 }
 
@@ -361,15 +315,8 @@ static int tcct_dice_ds_fwd_impl(const void* logits, int dtype, const uint8_t* l
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C * (1 + nlow), st) != hipSuccess) { tcct_set_error("dice_ds_fwd: memset failed"); return -2; }
     const int64_t M = (int64_t)B * H * W;
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_dice_sums<T>, dim3(tcct_grid(M, DSB, 512)), dim3(DSB), 0, st, (const T*)logits, labels, M, C, sums));
-    for (int i = 0; i < nlow; ++i) {
-        const int h = lh[i], w = lw[i], Sc = h > 0 ? H / h : 0;
-        TCCT_CHECK(h >= 1 && w >= 1 && H == Sc * h && W == Sc * w && (Sc == 2 || Sc == 4 || Sc == 8 || Sc == 16),
-                   "dice_ds_fwd: head %d needs an integer scale 2/4/8/16 (got %dx%d -> %dx%d)", i + 1, h, w, H, W);
-        TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "dice_ds_fwd: tensor too large");
-        double* sm = sums + (size_t)(i + 1) * 3 * C;
-        const float* low = lows[i];
-        UPDICE_SCALES(Sc, hipLaunchKernelGGL(k_updice_sums<S>, dim3(tcct_grid((int64_t)B * H * w, UDB, 512)), dim3(UDB), 0, st, low, labels, B, h, w, H, W, C, (float)h / (float)H, sm));
-    }
+    for (int i = 0; i < nlow; ++i)
+        if (int rc = dice_launch_upsums("dice_ds_fwd", lows[i], labels, B, lh[i], lw[i], H, W, C, sums + (size_t)(i + 1) * 3 * C, st)) return rc;
     hipLaunchKernelGGL(k_dice_finalize_ds, dim3(1), dim3(64), 0, st, sums, C, 1 + nlow, coff, loss);
     TCCT_LAUNCH_OK();
 }

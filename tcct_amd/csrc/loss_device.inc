@@ -1,5 +1,7 @@
-// Device helpers shared by the Dice kernels (loss_classes.inc) and the criterion family (crit_classes.inc): the per-pixel softmax, the lane-exchange row
-// interpolation of the upsampled heads and pass 2 of their backward.  Included INSIDE the per-MAXC namespace of either file (uses MAXC).  NOT a stand-alone translation unit.
+// What the three criterion families (Dice: loss_classes.inc, crit: crit_classes.inc, mcrit: mcrit_classes.inc) have in common, ONCE: the per-pixel softmax, the block tail
+// of the sums kernels, the lane-exchange row interpolation of the upsampled heads, pass 2 of their backward, and the host-side argument check / pass-2 launch.  The
+// kernels keep their names, signatures and loops (batch-global families flatten B*H*w, mcrit works inside blockIdx.y = n).  Included INSIDE the per-MAXC namespace of each
+// file (uses MAXC).  NOT a stand-alone translation unit.
 __device__ __forceinline__ void softmax_inplace(float (&z)[MAXC], int C) {
     float mx = -INFINITY, s = 0.f;
 #pragma unroll
@@ -9,6 +11,33 @@ __device__ __forceinline__ void softmax_inplace(float (&z)[MAXC], int C) {
     const float inv = __builtin_amdgcn_rcpf(s);      // (v_rcp_f32, 1 ulp: the IEEE division is ten instructions per pixel)
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) z[c] *= inv;
+}
+// Block tail of every sums kernel: wave sums -> LDS -> ONE fp64 atomic per (slot, class) and block.  The atomics serialise per address (see norm.hip), which is why these
+// kernels run 1024-thread blocks on <= 512 blocks.  `hook` decides per slot whether it is written at all and may scale the block's total of a class (mcrit's
+// cross-entropy: no slot 1, the class weight once per block).
+struct TailPlain {
+    __device__ __forceinline__ bool keep(int) const { return true; }
+    __device__ __forceinline__ double scale(int, double a) const { return a; }
+};
+template <int NB, typename Hook = TailPlain>
+__device__ __forceinline__ void sums_block_tail(const float (&A)[MAXC], const float (&P)[MAXC], const float (&G)[MAXC], int C, double* __restrict__ sums /*[3][C]*/,
+                                                Hook hook = Hook()) {
+    __shared__ float sm[3 * MAXC][NB / 64];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        float a = wave_sum(A[c]), b = wave_sum(P[c]), g = wave_sum(G[c]);
+        if (lane == 0) { sm[c][w] = a; sm[MAXC + c][w] = b; sm[2 * MAXC + c][w] = g; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * MAXC) {
+        int q = threadIdx.x / MAXC, c = threadIdx.x % MAXC;
+        if (c < C && hook.keep(q)) {
+            double a = 0.0;
+            for (int k = 0; k < NB / 64; ++k) a += (double)sm[threadIdx.x][k];
+            atomicAdd(&sums[q * C + c], hook.scale(c, a));
+        }
+    }
 }
 #define UDB 1024     // <= 512 blocks (the fp64 atomics of the tail serialise per address), so large blocks for occupancy
 // A thread owns low-res column j of one full-resolution row: the S pixels p = S j + k (forward) or the 2S pixels S j - S/2 + k that touch
@@ -62,9 +91,20 @@ __device__ __forceinline__ void updice_pixel(const float (&R)[3][MAXC], int kk /
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) z[c] = c < C ? l0 * R[q][c] + l1 * R[q + 1][c] : -INFINITY;
 }
+// The S pixels of an item sit in a `#pragma unroll` loop of the KERNEL, never of a helper: with that loop inside an inlined function the compiler keeps the per-class
+// accumulators in another form and needs up to 30 % more registers (measured on every family), so the item bodies of the sums kernels and of pass 1 of the backward are
+// calls of updice_rows / updice_pixel / softmax_inplace written out in each kernel.
 #define UPDICE_SCALES(S_, STMT) \
     do { if (S_ == 2) { constexpr int S = 2; STMT; } else if (S_ == 4) { constexpr int S = 4; STMT; } else if (S_ == 8) { constexpr int S = 8; STMT; } \
          else { constexpr int S = 16; STMT; } } while (0)
+// the argument check of every upsampled head: an integer scale 2/4/8/16 (-> *Sc) and item counts that fit the kernels' 32-bit indices
+static int upsampled_args_ok(const char* what, int B, int h, int w, int H, int W, int* Sc) {
+    *Sc = h > 0 ? H / h : 0;
+    TCCT_CHECK(B >= 1 && h >= 1 && w >= 1 && H == *Sc * h && W == *Sc * w && (*Sc == 2 || *Sc == 4 || *Sc == 8 || *Sc == 16),
+               "%s: needs an integer scale 2/4/8/16 (got %dx%d -> %dx%d)", what, h, w, H, W);
+    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "%s: tensor too large", what);
+    return 0;
+}
 // pass 2: dlow[n, i, j, c] = sum_ho wh(ho, i) T[n, ho, j, c]
 __global__ void k_updice_bwd_h(const float* __restrict__ T, int B, int h, int wC, int H, int S, float sh, float* __restrict__ dlow) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -80,4 +120,9 @@ __global__ void k_updice_bwd_h(const float* __restrict__ T, int B, int h, int wC
         }
         dlow[(int64_t)row * wC + e] = acc;
     }
+}
+static void launch_updice_bwd_h(const float* ws, int B, int h, int w, int C, int H, int S, float* dlow, hipStream_t st) {
+    const int wC = w * C, gx2 = (wC + 255) / 256;
+    int gy2 = B * h; if (gy2 > 65535) gy2 = 65535;
+    hipLaunchKernelGGL(k_updice_bwd_h, dim3(gx2, gy2), dim3(256), 0, st, ws, B, h, wC, H, S, (float)h / (float)H, dlow);
 }

@@ -9,6 +9,8 @@
 // A block works inside ONE sample (blockIdx.y = n, as k_confusion): a thread's accumulators never cross a sample boundary.
 // d L / d p_c = k0[n][c] + [c == label] k2[n][c] for dice / dice2 / iou (mcrit_grad_coeffs, from the sample's own sums); cross-entropy is written in logits directly,
 // d L / d z_c = (w_l / W_tot) (p_c - [c == l]) -- never through d L / d p, which divides by p_l.
+// This file holds the family's own arithmetic (mcrit_accum, McritTail, mcrit_grad_coeffs, mcrit_pixel_grad, the finalisation) and its kernels' outer loops inside one sample;
+// the shared pieces are loss_device.inc's.
 namespace MCNS {
 #include "loss_device.inc"
 
@@ -45,28 +47,13 @@ __device__ __forceinline__ void mcrit_accum(float (&z)[MAXC], int C, int l, floa
         }
     }
 }
-// crit_block_tail: wave sums -> LDS -> one fp64 atomic per (slot, class) and block (<= 512 blocks per sample row of the sums buffer: the atomics serialise per address)
-template <int NB, int KIND>
-__device__ __forceinline__ void mcrit_block_tail(const float (&A)[MAXC], const float (&P)[MAXC], const float (&G)[MAXC], int C, const float* __restrict__ class_w,
-                                                 double* __restrict__ sums /* the sample's [3][C] */) {
-    __shared__ float sm[3 * MAXC][NB / 64];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        float a = wave_sum(A[c]), b = wave_sum(P[c]), g = wave_sum(G[c]);
-        if (lane == 0) { sm[c][w] = a; sm[MAXC + c][w] = b; sm[2 * MAXC + c][w] = g; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 * MAXC) {
-        int q = threadIdx.x / MAXC, c = threadIdx.x % MAXC;
-        if (c < C && !(KIND == TCCT_MCRIT_CE && q == 1)) {
-            double a = 0.0;
-            for (int k = 0; k < NB / 64; ++k) a += (double)sm[threadIdx.x][k];
-            if (KIND == TCCT_MCRIT_CE && class_w) a *= (double)class_w[c];
-            atomicAdd(&sums[q * C + c], a);
-        }
-    }
-}
+// hook of sums_block_tail (<= 512 blocks per sample row of the sums buffer): cross-entropy has no slot 1 and takes its class weight here, once per block
+template <int KIND>
+struct McritTail {
+    const float* __restrict__ class_w;
+    __device__ __forceinline__ bool keep(int q) const { return !(KIND == TCCT_MCRIT_CE && q == 1); }
+    __device__ __forceinline__ double scale(int c, double a) const { return KIND == TCCT_MCRIT_CE && class_w ? a * (double)class_w[c] : a; }
+};
 
 #define MSB 1024
 template <typename T, int KIND>
@@ -84,7 +71,7 @@ __global__ void __launch_bounds__(MSB) k_mcrit_sums(const T* __restrict__ logits
         for (int c = 0; c < MAXC; ++c) z[c] = c < C ? ldf(lg + i * C + c) : -INFINITY;
         mcrit_accum<KIND>(z, C, lb[i], A, P, G);
     }
-    mcrit_block_tail<MSB, KIND>(A, P, G, C, class_w, sums + (size_t)n * 3 * C);
+    sums_block_tail<MSB>(A, P, G, C, sums + (size_t)n * 3 * C, McritTail<KIND>{class_w});
 }
 // k_upcrit_sums with the item loop inside one sample: a lane owns low-resolution column j of one full-resolution row of sample blockIdx.y
 template <int S, int KIND>
@@ -100,9 +87,8 @@ __global__ void __launch_bounds__(UDB) k_upmcrit_sums(const float* __restrict__ 
         const bool live = base + (int)(threadIdx.x & 63) < items;
         const int it = live ? base + (int)(threadIdx.x & 63) : items - 1;
         const int ho = (int)udiv32(it, w, m_w), j = it - ho * w;
-        const Lerp a = src_index(ho, sh, h, 0);
         float R[3][MAXC];
-        updice_rows<S>(low, n, h, w, C, a, j, R, live);
+        updice_rows<S>(low, n, h, w, C, src_index(ho, sh, h, 0), j, R, live);
         if (!live) continue;
         const uint8_t* lr = lab + ((int64_t)n * H + ho) * W + S * j;
 #pragma unroll
@@ -112,7 +98,7 @@ __global__ void __launch_bounds__(UDB) k_upmcrit_sums(const float* __restrict__ 
             mcrit_accum<KIND>(z, C, lr[k], A, P, G);
         }
     }
-    mcrit_block_tail<UDB, KIND>(A, P, G, C, class_w, sums + (size_t)n * 3 * C);
+    sums_block_tail<UDB>(A, P, G, C, sums + (size_t)n * 3 * C, McritTail<KIND>{class_w});
 }
 
 // the summand of (sample, class): dice 2 (A + s) / (P + G + s), dice2 that plus the same on the complements, iou A / (P + G - A + s)
@@ -226,10 +212,9 @@ __global__ void __launch_bounds__(LB) k_mcrit_bwd(const T* __restrict__ logits, 
             if (c < C) stf(dl + i * C + c, g[c]);
     }
 }
-// KEEP IN STEP with k_updice_bwd_w (loss_classes.inc) and k_upcrit_bwd_w (crit_classes.inc): this is that kernel with the wave loop inside one sample (blockIdx.y = n)
-// and mcrit_pixel_grad in place of their gradient; an edit of the halo lanes, the border clamps or the exchange belongs in all three.
-// pass 1 of the upsampled backward: every pixel evaluated once by the lane that owns its low-resolution column, the foreign tap's share travels to the adjacent lane,
-// 62 columns + 2 halo lanes per wave; pass 2 is k_updice_bwd_h itself
+// pass 1 of the upsampled backward: k_updice_bwd_w (loss_classes.inc, where the scheme is explained) with the wave loop inside one sample (blockIdx.y = n) and
+// mcrit_pixel_grad as the gradient; pass 2 is k_updice_bwd_h itself.  Written out like its two siblings (see k_upcrit_bwd_w in crit_classes.inc for why): a change of
+// the halo lanes, the border clamps or the exchange is made in all three.
 template <int S>
 __global__ void __launch_bounds__(256) k_upmcrit_bwd_w(const float* __restrict__ low, const uint8_t* __restrict__ lab, int B, int h, int w, int H, int W, int C, float sh,
                                                        int kind, const float* __restrict__ class_w, const double* __restrict__ sums, const float* __restrict__ gout,
@@ -297,10 +282,8 @@ __global__ void __launch_bounds__(256) k_upmcrit_bwd_w(const float* __restrict__
     TCCT_CHECK(kind >= TCCT_MCRIT_DICE && kind <= TCCT_MCRIT_CE, what ": kind=%d unknown (0 dice, 1 dice2, 2 iou, 3 ce)", kind); \
     TCCT_CHECK(B >= 1 && B <= 65535, what ": batch %d unsupported (1..65535)", B)
 #define MCRIT_UP_OK(what) \
-    const int Sc = h > 0 ? H / h : 0; \
-    TCCT_CHECK(h >= 1 && w >= 1 && H == Sc * h && W == Sc * w && (Sc == 2 || Sc == 4 || Sc == 8 || Sc == 16), \
-               what ": needs an integer scale 2/4/8/16 (got %dx%d -> %dx%d)", h, w, H, W); \
-    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), what ": tensor too large")
+    int Sc; \
+    if (int rc = upsampled_args_ok(what, B, h, w, H, W, &Sc)) return rc
 
 // blocks per sample of the sums kernels: ~512 blocks for the whole batch, as the batch-global siblings launch (never more than 512 per sample row of the sums buffer).
 // Measured at bs 8, 800 x 1104: with 512 blocks PER SAMPLE a thread saw 1.7 pixels and the launch was all block tail (45 wave sums, 15 fp64 atomics per block).
@@ -354,9 +337,7 @@ static int tcct_upmcrit_bwd_impl(const float* low, const uint8_t* labels, int B,
     const int gx = tcct_grid((int64_t)H * ((w + 61) / 62), 4, B >= (1 << 14) ? 1 : (1 << 14) / B);
     UPDICE_SCALES(Sc, hipLaunchKernelGGL(k_upmcrit_bwd_w<S>, dim3(gx, B), dim3(256), 0, st, low, labels, B, h, w, H, W, C, (float)h / (float)H, kind, class_w, sums, grad_out,
                                          grad_scale, ws));
-    const int wC = w * C, gx2 = (wC + 255) / 256;
-    int gy2 = B * h; if (gy2 > 65535) gy2 = 65535;
-    hipLaunchKernelGGL(k_updice_bwd_h, dim3(gx2, gy2), dim3(256), 0, st, ws, B, h, wC, H, Sc, (float)h / (float)H, dlow);
+    launch_updice_bwd_h(ws, B, h, w, C, H, Sc, dlow, st);
     TCCT_LAUNCH_OK();
 }
 // the deep-supervision criterion as one launch sequence (tcct_crit_ds_fwd's layout): sums fp64 [(1 + nlow)][B][3][C], head 0 = the full-resolution one

@@ -3186,27 +3186,135 @@ def norm_add6(a0, b0, a1, b1, a2, b2, eps=1e-12):
 
 
 # ------------------------------------------------------------------------------------------------ losses
-class _SoftmaxDice(_FastFunction):
-    @staticmethod
-    def forward(ctx, logits, labels):
+# Three criterion families run the same three nodes (full resolution, upsampled head, deep supervision) over their own kernels:
+#   'dice'   MultiLoss(DiceLoss), the benchmark's path               tcct_softmax_dice_*,  tcct_updice_*,  tcct_dice_ds_fwd    (csrc/loss.hip)
+#   'crit'   MultiLoss dice / dice2 / iou / mse + class weights      tcct_softmax_crit_*,  tcct_upcrit_*,  tcct_crit_ds_fwd    (csrc/crit.hip)
+#   'mcrit'  get_mloss per-sample dice / dice2 / iou, cross-entropy  tcct_softmax_mcrit_*, tcct_upmcrit_*, tcct_mcrit_ds_fwd   (csrc/mcrit.hip)
+class _LossFamily:
+    """What the families differ in on this side of the C-ABI.  Everything is fixed when the record is made, except the entry points themselves: the library loads lazily,
+    so `fwd`, `bwd`, `up_fwd`, `up_bwd`, `ds_fwd` are bound on first use and are plain attributes from then on (what `lib.<name>` itself does)."""
+
+    def __init__(self, tag, n_extra, per_sample):
+        self.names = {'fwd': f'softmax_{tag}_fwd', 'bwd': f'softmax_{tag}_bwd', 'up_fwd': f'up{tag}_fwd', 'up_bwd': f'up{tag}_bwd', 'ds_fwd': f'{tag}_ds_fwd'}
+        self.n_extra = n_extra                      # 2: (kind code, class_w) follow C in every call and the node's own arguments in `apply`; 0: Dice has neither
+        if per_sample:                              # sums of a head fp64 [B][3][C], the full-resolution entry points take (B, HW)
+            self.per_head, self.lead = (lambda B, C: B * 3 * C), (lambda B, n: (B, n // B))
+        else:                                       # sums of a head fp64 [3][C], the full-resolution entry points take M = B * HW
+            self.per_head, self.lead = (lambda B, C: 3 * C), (lambda B, n: (n,))
+
+    def __getattr__(self, name):
+        fn = getattr(lib, self.names[name])
+        self.__dict__[name] = fn
+        return fn
+
+
+def _softmax_node(name, fam, doc=None):
+    """<criterion>(logits NHWC [B,..,C], labels uint8): apply(logits, labels, *extra)"""
+    nones = (None,) * (1 + fam.n_extra)
+
+    def forward(ctx, logits, labels, *extra):
         _chk(logits, labels)
-        C = logits.shape[-1]
-        M = logits.numel() // C
-        sums = torch.empty(3 * C, device=logits.device, dtype=torch.float64)
+        B, C = logits.shape[0], logits.shape[-1]
+        sums = torch.empty(fam.per_head(B, C), device=logits.device, dtype=torch.float64)
         loss = torch.empty((), device=logits.device, dtype=torch.float32)
-        lib.softmax_dice_fwd(logits, labels, M, C, sums, loss, dtype_code(logits.dtype))
+        fam.fwd(logits, labels, *fam.lead(B, logits.numel() // C), C, *extra, sums, loss, dtype_code(logits.dtype))
         ctx.save_for_backward(logits, labels, sums)
+        ctx.cfg = extra
         return loss
 
-    @staticmethod
     def backward(ctx, g):
         logits, labels, sums = ctx.saved_tensors
-        C = logits.shape[-1]
-        M = logits.numel() // C
+        B, C = logits.shape[0], logits.shape[-1]
         g = _as(g, torch.float32)
         d = torch.empty_like(logits)
-        lib.softmax_dice_bwd(logits, labels, M, C, sums, g, 1.0, d, dtype_code(logits.dtype))
-        return d, None
+        fam.bwd(logits, labels, *fam.lead(B, logits.numel() // C), C, *ctx.cfg, sums, g, 1.0, d, dtype_code(logits.dtype))
+        return (d,) + nones
+
+    return type(name, (_FastFunction,), {'forward': staticmethod(forward), 'backward': staticmethod(backward), '__doc__': doc})
+
+
+def _upsampled_node(name, fam, doc):
+    """<criterion>(F.interpolate(low, (H, W), 'bilinear'), labels) without materialising the resized logits (deep-supervision heads): apply(low, labels, H, W, *extra)"""
+    nones = (None,) * (3 + fam.n_extra)
+
+    def forward(ctx, low, labels, H, W, *extra):
+        _chk(low, labels)
+        B, h, w, C = low.shape
+        sums = torch.empty(fam.per_head(B, C), device=low.device, dtype=torch.float64)
+        loss = torch.empty((), device=low.device, dtype=torch.float32)
+        fam.up_fwd(low, labels, B, h, w, H, W, C, *extra, sums, loss)
+        ctx.save_for_backward(low, labels, sums)
+        ctx.cfg = (H, W, extra)
+        return loss
+
+    def backward(ctx, g):
+        low, labels, sums = ctx.saved_tensors
+        B, h, w, C = low.shape
+        H, W, extra = ctx.cfg
+        g = _as(g, torch.float32)
+        ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
+        d = torch.empty_like(low)
+        fam.up_bwd(low, labels, B, h, w, H, W, C, *extra, sums, g, 1.0, ws, d)
+        return (d,) + nones
+
+    return type(name, (_FastFunction,), {'forward': staticmethod(forward), 'backward': staticmethod(backward), '__doc__': doc})
+
+
+def _deep_supervision_node(name, fam, doc):
+    """sum_{i = n..1} coff * <criterion>(resize(low_i)) + <criterion>(logits0) as ONE node: apply(logits0, labels, coff, H, W, *extra, *lows).  sums: head i at
+    [i * per_head, (i + 1) * per_head), head 0 = the full-resolution one; the backward kernels of the low-resolution heads take coff as their grad_scale."""
+    n_extra = fam.n_extra
+    nones = (None,) * (4 + n_extra)
+
+    def forward(ctx, logits0, labels, coff, H, W, *rest):
+        extra, lows = rest[:n_extra], rest[n_extra:]
+        _chk(logits0, labels, *lows)
+        B, _, _, C = logits0.shape
+        sums = torch.empty(4 * fam.per_head(B, C), device=logits0.device, dtype=torch.float64)
+        loss = torch.empty((), device=logits0.device, dtype=torch.float32)
+        a = []
+        for i in range(3):
+            a += [lows[i], lows[i].shape[1], lows[i].shape[2]] if i < len(lows) else [None, 0, 0]
+        fam.ds_fwd(logits0, dtype_code(logits0.dtype), labels, B, H, W, C, *a, coff, *extra, sums, loss)
+        ctx.save_for_backward(logits0, labels, sums, *lows)
+        ctx.cfg = (coff, H, W, extra)
+        return loss
+
+    def backward(ctx, g):
+        logits0, labels, sums, *lows = ctx.saved_tensors
+        coff, H, W, extra = ctx.cfg
+        B, _, _, C = logits0.shape
+        per = fam.per_head(B, C)
+        g = _as(g, torch.float32)
+        d0 = torch.empty_like(logits0)
+        fam.bwd(logits0, labels, *fam.lead(B, logits0.numel() // C), C, *extra, sums[:per], g, 1.0, d0, dtype_code(logits0.dtype))
+        dl = []
+        for i, low in enumerate(lows):
+            _, h, w, _ = low.shape
+            ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
+            d = torch.empty_like(low)
+            fam.up_bwd(low, labels, B, h, w, H, W, C, *extra, sums[(i + 1) * per:(i + 2) * per], g, coff, ws, d)
+            dl.append(d)
+        return (d0,) + nones + tuple(dl)
+
+    return type(name, (_FastFunction,), {'forward': staticmethod(forward), 'backward': staticmethod(backward), '__doc__': doc})
+
+
+_DICE, _CRIT, _MCRIT = _LossFamily('dice', 0, False), _LossFamily('crit', 2, False), _LossFamily('mcrit', 2, True)
+
+_SoftmaxDice = _softmax_node('_SoftmaxDice', _DICE)
+_UpDice = _upsampled_node('_UpDice', _DICE, """MultiLoss(DiceLoss)(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits (deep-supervision heads)""")
+_DeepSupervisionDice = _deep_supervision_node('_DeepSupervisionDice', _DICE, """KiteSeg.grad_calc with MultiLoss(DiceLoss) (reference kite/loopback.py:62-73):
+    sum_{i=3,2,1} coff * Dice(resize(low_i)) + Dice(logits0) as ONE node: one memset, four sums kernels, one finalisation; the scalar multiplications and additions of the
+    loop (a dozen 5-us launches on the single-stream stretch of the step, each way) are arithmetic inside the finalisation kernel / the grad_scale argument of the backward
+    kernels.""")
+_SoftmaxCrit = _softmax_node('_SoftmaxCrit', _CRIT)
+_UpCrit = _upsampled_node('_UpCrit', _CRIT, """MultiLoss(<kind>, weight)(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits""")
+_DeepSupervisionCrit = _deep_supervision_node('_DeepSupervisionCrit', _CRIT, """_DeepSupervisionDice for every criterion kind / class weights: one memset, up to four sums kernels,
+    one finalisation""")
+_SoftmaxMCrit = _softmax_node('_SoftmaxMCrit', _MCRIT)
+_UpMCrit = _upsampled_node('_UpMCrit', _MCRIT, """<m-criterion>(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits""")
+_DeepSupervisionMCrit = _deep_supervision_node('_DeepSupervisionMCrit', _MCRIT, """_DeepSupervisionCrit for the m-criteria: one memset, up to four sums kernels, one finalisation""")
 
 
 def softmax_dice(logits, labels):
@@ -3214,169 +3322,36 @@ def softmax_dice(logits, labels):
     return _SoftmaxDice.apply(logits, labels)
 
 
-class _UpDice(_FastFunction):
-    """MultiLoss(DiceLoss)(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits (deep-supervision heads)"""
-
-    @staticmethod
-    def forward(ctx, low, labels, H, W):
-        _chk(low, labels)
-        B, h, w, C = low.shape
-        sums = torch.empty(3 * C, device=low.device, dtype=torch.float64)
-        loss = torch.empty((), device=low.device, dtype=torch.float32)
-        lib.updice_fwd(low, labels, B, h, w, H, W, C, sums, loss)
-        ctx.save_for_backward(low, labels, sums)
-        ctx.size = (H, W)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, labels, sums = ctx.saved_tensors
-        B, h, w, C = low.shape
-        H, W = ctx.size
-        g = _as(g, torch.float32)
-        ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
-        d = torch.empty_like(low)
-        lib.updice_bwd(low, labels, B, h, w, H, W, C, sums, g, 1.0, ws, d)
-        return d, None, None, None
-
-
-class _DeepSupervisionDice(_FastFunction):
-    """KiteSeg.grad_calc with MultiLoss(DiceLoss) (reference kite/loopback.py:62-73): sum_{i=3,2,1} coff * Dice(resize(low_i)) + Dice(logits0) as ONE node: one
-    memset, four sums kernels, one finalisation; the scalar multiplications and additions of the loop (a dozen 5-us launches on the single-stream stretch of the
-    step, each way) are arithmetic inside the finalisation kernel / the grad_scale argument of the backward kernels."""
-
-    @staticmethod
-    def forward(ctx, logits0, labels, coff, H, W, *lows):
-        _chk(logits0, labels, *lows)
-        B, _, _, C = logits0.shape
-        sums = torch.empty(4 * 3 * C, device=logits0.device, dtype=torch.float64)
-        loss = torch.empty((), device=logits0.device, dtype=torch.float32)
-        a = []
-        for i in range(3):
-            a += [lows[i], lows[i].shape[1], lows[i].shape[2]] if i < len(lows) else [None, 0, 0]
-        lib.dice_ds_fwd(logits0, dtype_code(logits0.dtype), labels, B, H, W, C, *a, coff, sums, loss)
-        ctx.save_for_backward(logits0, labels, sums, *lows)
-        ctx.cfg = (coff, H, W)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits0, labels, sums, *lows = ctx.saved_tensors
-        coff, H, W = ctx.cfg
-        B, _, _, C = logits0.shape
-        g = _as(g, torch.float32)
-        d0 = torch.empty_like(logits0)
-        lib.softmax_dice_bwd(logits0, labels, logits0.numel() // C, C, sums[:3 * C], g, 1.0, d0, dtype_code(logits0.dtype))
-        dl = []
-        for i, low in enumerate(lows):
-            _, h, w, _ = low.shape
-            ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
-            d = torch.empty_like(low)
-            lib.updice_bwd(low, labels, B, h, w, H, W, C, sums[(i + 1) * 3 * C:(i + 2) * 3 * C], g, coff, ws, d)
-            dl.append(d)
-        return (d0, None, None, None, None) + tuple(dl)
-
-
-# The criterion family of the reference's MultiLoss (kite/losses/loss.py:9-110): per-class loss `kind` + per-class weights.  kind 'dice' without weights IS the nodes
-# above (the benchmark's path, untouched); everything else runs the tcct_softmax_crit_* / tcct_upcrit_* / tcct_crit_ds_fwd kernels (csrc/crit.hip).
+# The criterion family of the reference's MultiLoss (kite/losses/loss.py:9-110): per-class loss `kind` + per-class weights.  kind 'dice' without weights IS the Dice
+# family (the benchmark's path, untouched); everything else runs the tcct_softmax_crit_* / tcct_upcrit_* / tcct_crit_ds_fwd kernels (csrc/crit.hip).
 CRIT_KINDS = {'dice': 0, 'dice2': 1, 'iou': 2, 'mse': 3}
+# The criteria of the reference's get_mloss (kite/losses/lossm.py over kite/losses/miou.py): Dice / dice2 / IoU taken per SAMPLE and per class, and
+# nn.CrossEntropyLoss(weight) -- tcct_softmax_mcrit_* / tcct_upmcrit_* / tcct_mcrit_ds_fwd (csrc/mcrit.hip).  sums fp64 [head][B][3][C].
+MCRIT_KINDS = {'dice': 0, 'dice2': 1, 'iou': 2, 'ce': 3}
+
+
+def _class_w_ok(class_w, C, device):
+    """The weights are read by the kernels at run time (a persistent buffer of the caller: graph-capturable)."""
+    if class_w is not None and not (torch.is_tensor(class_w) and class_w.dtype == torch.float32 and class_w.dim() == 1 and class_w.numel() >= C
+                                    and class_w.is_contiguous() and class_w.device == device):
+        raise TcctError(f'class weights: a contiguous fp32 vector of at least {C} entries on {device} is needed')
+    return class_w
 
 
 def _crit_args(kind, class_w, C, device):
-    """-> (kind code, fp32 [C] weights on `device` or None).  The weights are read by the kernels at run time (a persistent buffer of the caller: graph-capturable)."""
+    """-> (kind code, fp32 [C] weights on `device` or None)"""
     if kind not in CRIT_KINDS:
         raise TcctError(f'criterion kind {kind!r}: one of {sorted(CRIT_KINDS)}')
-    if class_w is not None:
-        if not (torch.is_tensor(class_w) and class_w.dtype == torch.float32 and class_w.dim() == 1 and class_w.numel() >= C and class_w.is_contiguous()
-                and class_w.device == device):
-            raise TcctError(f'class weights: a contiguous fp32 vector of at least {C} entries on {device} is needed')
-    return CRIT_KINDS[kind], class_w
+    return CRIT_KINDS[kind], _class_w_ok(class_w, C, device)
 
 
-class _SoftmaxCrit(_FastFunction):
-    @staticmethod
-    def forward(ctx, logits, labels, kind, class_w):
-        _chk(logits, labels)
-        C = logits.shape[-1]
-        M = logits.numel() // C
-        sums = torch.empty(3 * C, device=logits.device, dtype=torch.float64)
-        loss = torch.empty((), device=logits.device, dtype=torch.float32)
-        lib.softmax_crit_fwd(logits, labels, M, C, kind, class_w, sums, loss, dtype_code(logits.dtype))
-        ctx.save_for_backward(logits, labels, sums)
-        ctx.cfg = (kind, class_w)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, labels, sums = ctx.saved_tensors
-        kind, class_w = ctx.cfg
-        C = logits.shape[-1]
-        M = logits.numel() // C
-        g = _as(g, torch.float32)
-        d = torch.empty_like(logits)
-        lib.softmax_crit_bwd(logits, labels, M, C, kind, class_w, sums, g, 1.0, d, dtype_code(logits.dtype))
-        return d, None, None, None
-
-
-class _UpCrit(_FastFunction):
-    """MultiLoss(<kind>, weight)(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits"""
-
-    @staticmethod
-    def forward(ctx, low, labels, H, W, kind, class_w):
-        _chk(low, labels)
-        B, h, w, C = low.shape
-        sums = torch.empty(3 * C, device=low.device, dtype=torch.float64)
-        loss = torch.empty((), device=low.device, dtype=torch.float32)
-        lib.upcrit_fwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, loss)
-        ctx.save_for_backward(low, labels, sums)
-        ctx.cfg = (H, W, kind, class_w)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, labels, sums = ctx.saved_tensors
-        B, h, w, C = low.shape
-        H, W, kind, class_w = ctx.cfg
-        g = _as(g, torch.float32)
-        ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
-        d = torch.empty_like(low)
-        lib.upcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, g, 1.0, ws, d)
-        return d, None, None, None, None, None
-
-
-class _DeepSupervisionCrit(_FastFunction):
-    """_DeepSupervisionDice for every criterion kind / class weights: one memset, up to four sums kernels, one finalisation"""
-
-    @staticmethod
-    def forward(ctx, logits0, labels, coff, H, W, kind, class_w, *lows):
-        _chk(logits0, labels, *lows)
-        B, _, _, C = logits0.shape
-        sums = torch.empty(4 * 3 * C, device=logits0.device, dtype=torch.float64)
-        loss = torch.empty((), device=logits0.device, dtype=torch.float32)
-        a = []
-        for i in range(3):
-            a += [lows[i], lows[i].shape[1], lows[i].shape[2]] if i < len(lows) else [None, 0, 0]
-        lib.crit_ds_fwd(logits0, dtype_code(logits0.dtype), labels, B, H, W, C, *a, coff, kind, class_w, sums, loss)
-        ctx.save_for_backward(logits0, labels, sums, *lows)
-        ctx.cfg = (coff, H, W, kind, class_w)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits0, labels, sums, *lows = ctx.saved_tensors
-        coff, H, W, kind, class_w = ctx.cfg
-        B, _, _, C = logits0.shape
-        g = _as(g, torch.float32)
-        d0 = torch.empty_like(logits0)
-        lib.softmax_crit_bwd(logits0, labels, logits0.numel() // C, C, kind, class_w, sums[:3 * C], g, 1.0, d0, dtype_code(logits0.dtype))
-        dl = []
-        for i, low in enumerate(lows):
-            _, h, w, _ = low.shape
-            ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
-            d = torch.empty_like(low)
-            lib.upcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums[(i + 1) * 3 * C:(i + 2) * 3 * C], g, coff, ws, d)
-            dl.append(d)
-        return (d0, None, None, None, None, None, None) + tuple(dl)
+def _mcrit_args(kind, class_w, C, device):
+    """-> (kind code, class_w).  Only 'ce' takes class weights: the reference's MDiceLoss / MIouLoss have none."""
+    if kind not in MCRIT_KINDS:
+        raise TcctError(f'm-criterion kind {kind!r}: one of {sorted(MCRIT_KINDS)}')
+    if class_w is not None and kind != 'ce':
+        raise TcctError(f'm-criterion kind {kind!r} takes no class weights (only \'ce\' does)')
+    return MCRIT_KINDS[kind], _class_w_ok(class_w, C, device)
 
 
 def softmax_criterion(logits, labels, kind='dice', class_w=None):
@@ -3405,111 +3380,6 @@ def deep_supervision_criterion(logits0_nhwc, labels, lows, coff, kind='dice', cl
     code, class_w = _crit_args(kind, class_w, logits0_nhwc.shape[-1], logits0_nhwc.device)
     H, W = lows[0].size
     return _DeepSupervisionCrit.apply(logits0_nhwc, labels, float(coff), H, W, code, class_w, *[l_.low for l_ in lows])
-
-
-# The criteria of the reference's get_mloss (kite/losses/lossm.py over kite/losses/miou.py): Dice / dice2 / IoU taken per SAMPLE and per class, and
-# nn.CrossEntropyLoss(weight) -- tcct_softmax_mcrit_* / tcct_upmcrit_* / tcct_mcrit_ds_fwd (csrc/mcrit.hip).  sums fp64 [head][B][3][C].
-MCRIT_KINDS = {'dice': 0, 'dice2': 1, 'iou': 2, 'ce': 3}
-
-
-def _mcrit_args(kind, class_w, C, device):
-    """-> (kind code, class_w).  Only 'ce' takes class weights: the reference's MDiceLoss / MIouLoss have none."""
-    if kind not in MCRIT_KINDS:
-        raise TcctError(f'm-criterion kind {kind!r}: one of {sorted(MCRIT_KINDS)}')
-    if class_w is not None:
-        if kind != 'ce':
-            raise TcctError(f'm-criterion kind {kind!r} takes no class weights (only \'ce\' does)')
-        if not (torch.is_tensor(class_w) and class_w.dtype == torch.float32 and class_w.dim() == 1 and class_w.numel() >= C and class_w.is_contiguous()
-                and class_w.device == device):
-            raise TcctError(f'class weights: a contiguous fp32 vector of at least {C} entries on {device} is needed')
-    return MCRIT_KINDS[kind], class_w
-
-
-class _SoftmaxMCrit(_FastFunction):
-    @staticmethod
-    def forward(ctx, logits, labels, kind, class_w):
-        _chk(logits, labels)
-        B, C = logits.shape[0], logits.shape[-1]
-        HW = logits.numel() // (B * C)
-        sums = torch.empty(B * 3 * C, device=logits.device, dtype=torch.float64)
-        loss = torch.empty((), device=logits.device, dtype=torch.float32)
-        lib.softmax_mcrit_fwd(logits, labels, B, HW, C, kind, class_w, sums, loss, dtype_code(logits.dtype))
-        ctx.save_for_backward(logits, labels, sums)
-        ctx.cfg = (kind, class_w)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, labels, sums = ctx.saved_tensors
-        kind, class_w = ctx.cfg
-        B, C = logits.shape[0], logits.shape[-1]
-        HW = logits.numel() // (B * C)
-        g = _as(g, torch.float32)
-        d = torch.empty_like(logits)
-        lib.softmax_mcrit_bwd(logits, labels, B, HW, C, kind, class_w, sums, g, 1.0, d, dtype_code(logits.dtype))
-        return d, None, None, None
-
-
-class _UpMCrit(_FastFunction):
-    """<m-criterion>(F.interpolate(low, size, 'bilinear'), labels) without materialising the resized logits"""
-
-    @staticmethod
-    def forward(ctx, low, labels, H, W, kind, class_w):
-        _chk(low, labels)
-        B, h, w, C = low.shape
-        sums = torch.empty(B * 3 * C, device=low.device, dtype=torch.float64)
-        loss = torch.empty((), device=low.device, dtype=torch.float32)
-        lib.upmcrit_fwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, loss)
-        ctx.save_for_backward(low, labels, sums)
-        ctx.cfg = (H, W, kind, class_w)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, labels, sums = ctx.saved_tensors
-        B, h, w, C = low.shape
-        H, W, kind, class_w = ctx.cfg
-        g = _as(g, torch.float32)
-        ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
-        d = torch.empty_like(low)
-        lib.upmcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums, g, 1.0, ws, d)
-        return d, None, None, None, None, None
-
-
-class _DeepSupervisionMCrit(_FastFunction):
-    """_DeepSupervisionCrit for the m-criteria: one memset, up to four sums kernels, one finalisation"""
-
-    @staticmethod
-    def forward(ctx, logits0, labels, coff, H, W, kind, class_w, *lows):
-        _chk(logits0, labels, *lows)
-        B, _, _, C = logits0.shape
-        sums = torch.empty(4 * B * 3 * C, device=logits0.device, dtype=torch.float64)
-        loss = torch.empty((), device=logits0.device, dtype=torch.float32)
-        a = []
-        for i in range(3):
-            a += [lows[i], lows[i].shape[1], lows[i].shape[2]] if i < len(lows) else [None, 0, 0]
-        lib.mcrit_ds_fwd(logits0, dtype_code(logits0.dtype), labels, B, H, W, C, *a, coff, kind, class_w, sums, loss)
-        ctx.save_for_backward(logits0, labels, sums, *lows)
-        ctx.cfg = (coff, H, W, kind, class_w)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits0, labels, sums, *lows = ctx.saved_tensors
-        coff, H, W, kind, class_w = ctx.cfg
-        B, _, _, C = logits0.shape
-        per = B * 3 * C
-        g = _as(g, torch.float32)
-        d0 = torch.empty_like(logits0)
-        lib.softmax_mcrit_bwd(logits0, labels, B, H * W, C, kind, class_w, sums[:per], g, 1.0, d0, dtype_code(logits0.dtype))
-        dl = []
-        for i, low in enumerate(lows):
-            _, h, w, _ = low.shape
-            ws = torch.empty((B, H, w, C), device=low.device, dtype=torch.float32)
-            d = torch.empty_like(low)
-            lib.upmcrit_bwd(low, labels, B, h, w, H, W, C, kind, class_w, sums[(i + 1) * per:(i + 2) * per], g, coff, ws, d)
-            dl.append(d)
-        return (d0, None, None, None, None, None, None) + tuple(dl)
 
 
 def softmax_mcriterion(logits, labels, kind, class_w=None):
