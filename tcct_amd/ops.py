@@ -190,7 +190,6 @@ def step_streams():
     return out
 
 
-
 class _FastFunction(torch.autograd.Function):
     """torch.autograd.Function whose `apply` goes straight to the C++ implementation (round 6).  `Function.apply` first checks for a `setup_context` override, asks whether
     functorch transforms are active and runs `unwrap_dead_wrappers` over the arguments -- 6-8 us per call, ~130 calls per forward pass; the forward pass of the bench step is
@@ -242,8 +241,6 @@ def end_step():
 _WGRAD_USED = {}
 _WGRAD_KEEP = []
 DW_WGRAD_SIDE = True
-_WGRAD_FRESH_EVENT = False          # experiment on the late-capture crash
-_WGRAD_RECORD_STREAM = False      # the old behaviour, kept for A/B measurements only
 
 
 def fresh_stream(device=None, avoid=()):
@@ -276,8 +273,6 @@ class _wgrad_stream:
         if ent is None:         # the side stream and ONE reusable event for the cur -> side dependency (a wait captures the state of the
             ent = _SIDE_STREAMS[key] = (fresh_stream(cur.device), torch.cuda.Event())   # event at the time it is issued)
         self.side, ev = ent
-        if _WGRAD_FRESH_EVENT:
-            ev = torch.cuda.Event()
         ev.record(cur)
         self.side.wait_event(ev)
         # the block only launches this library's kernels into pre-allocated gradient slots: name the stream for them instead of
@@ -294,11 +289,7 @@ class _wgrad_stream:
         # end_step() has joined the side stream -- NOT tensor.record_stream(side): with every activation and gradient of the step
         # marked that way the caching allocator could not reuse a block until the side stream caught up, the host runs most of a
         # step ahead, and the reserved pool grew by ~3.5 GB per step (124 GB after 30 steps, then a multi-second free-and-retry stall)
-        if _WGRAD_RECORD_STREAM:
-            for t in self.tensors:
-                t.record_stream(self.side)
-        else:
-            _WGRAD_KEEP.extend(self.tensors)
+        _WGRAD_KEEP.extend(self.tensors)
         _WGRAD_USED[id(self.side)] = self.side
         return False
 
@@ -314,6 +305,11 @@ def _grad_out(param, shape=None):
     if slot is not None and ZERO.active:
         return slot.view(shape if shape is not None else slot.shape)
     return ZERO.get(tuple(shape if shape is not None else param.shape), torch.float32, param.device)
+
+
+def _zeros(shape, dtype, device):
+    """a zero-filled accumulation output: out of the step's pre-zeroed pool when one is active"""
+    return ZERO.get(shape, dtype, device) if ZERO.active else torch.zeros(shape, device=device, dtype=dtype)
 
 
 def _ret(t, param):
@@ -347,13 +343,6 @@ def _as(t, dtype):
 
 
 # ------------------------------------------------------------------------------------------------- conv
-def _mfma32_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-    """the MFMA implicit-GEMM kernel covers bf16 32->32 stride-1 'same' convolutions (3x3, 1xk, kx1)"""
-    return (in_dt == torch.bfloat16 and out_dt == torch.bfloat16 and Cin == 32 and Cin_w == 32 and Cout == 32 and stride == 1
-            and 2 * padh == KH - 1 and 2 * padw == KW - 1 and KH * KW > 1 and (KH == 1 or KW == 1 or (KH == 3 and KW == 3)))
-
-
-F32_MFMA = True        # False: the VALU convolution for the fp32 parity mode (A/B timing, bisecting)
 # fp32 MFMA for the pointwise forward / input gradient / weight gradient.  The FORWARD stays on the sequential VALU kernel in the parity mode: on
 # the formula-weight fixtures some BatchNorm channels at the 2x2 / 4x4 levels have a batch variance at fp32 rounding level, and the MFMA summation
 # order (exact to 2-5e-7 against fp64, like the VALU kernel's) moved rstd enough to scale the whole CNN level-0 gradient by 0.93 -- outside the
@@ -362,36 +351,76 @@ F32_MFMA = True        # False: the VALU convolution for the fp32 parity mode (A
 F32_PW = [os.environ.get('TCCT_F32_PW_FWD', '0') == '1', True, True]
 
 
-def _mfma32f_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-    """the fp32 MFMA kernels (conv_f32_mfma.hip) cover fp32 32->32 stride-1 'same' convolutions (3x3, 1xk, kx1, k <= 13) of the parity mode"""
-    return (F32_MFMA and in_dt == torch.float32 and out_dt == torch.float32 and Cin == 32 and Cin_w == 32 and Cout == 32 and stride == 1
-            and 2 * padh == KH - 1 and 2 * padw == KW - 1 and 1 < KH * KW <= 13 and (KH == 1 or KW == 1 or (KH == 3 and KW == 3)))
-
-
-def _pwf_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-    """fp32 MFMA pointwise kernels (conv_f32_mfma.hip): fp32 1x1 convolutions / Linear with channel counts that are multiples of 32"""
-    return (F32_MFMA and in_dt == torch.float32 and out_dt == torch.float32 and KH == 1 and KW == 1 and stride == 1 and padh == 0 and padw == 0
-            and Cin == Cin_w and Cin % 32 == 0 and Cout % 32 == 0)
-
-
-def _mfma_slabs_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-    """wider bf16 stride-1 'same' convolutions (3x3, 1xk, kx1 with channel counts that are multiples of 32) as 32x32 sub-GEMMs of the
-    conv32 kernels: MPViT stem[1] (32->64) and the wide CNN encoder of stc_tb / gtc_tb (32-64-96-128-256, nets/tcct.py:861-864)"""
-    return (in_dt == torch.bfloat16 and out_dt == torch.bfloat16 and Cin == Cin_w and Cin % 32 == 0 and Cout % 32 == 0
-            and 32 <= Cin <= 256 and 32 <= Cout <= 256 and (Cin, Cout) != (32, 32) and stride == 1
-            and 2 * padh == KH - 1 and 2 * padw == KW - 1 and KH * KW > 1 and max(KH, KW) <= 13
-            and (KH == 1 or KW == 1 or (KH == 3 and KW == 3)))
-
-
 # The 3x3 32 -> 64 convolution (MPViT stem[1], reference nets/tcct.py:682-689) as ONE launch per direction (tcct_conv32x64_fwd33 / tcct_conv64x32_dgrad33 /
 # tcct_conv32x64_wgrad33: wave pairs per strip, x / dy read from HBM once, dx rounded once) with its packs out of the one-launch-per-step registry.  The forward is
 # bit-identical to the slab path; TCCT_WIDE_CONV=0 restores the slab path (A/B timing).
 WIDE_CONV = os.environ.get('TCCT_WIDE_CONV', '1') != '0'
 
 
-def _wide33_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-    return (WIDE_CONV and in_dt == torch.bfloat16 and out_dt == torch.bfloat16 and Cin == 32 and Cin_w == 32 and Cout == 64 and KH == 3 and KW == 3
-            and stride == 1 and padh == 1 and padw == 1)
+def conv_route(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
+    """The kernel family of a convolution, from dtypes and integers alone (no tensor, no device) -- every direction of _Conv2d and conv_bn_act resolve from it
+    (conv_fwd_route / conv_dgrad_route / conv_wgrad_route), and a new family is one clause here plus one row of _CONV_ROUTES:
+      pw         bf16 input, 1x1 / Linear, Cin % 32 == 0: the MFMA pointwise kernels (any output dtype)
+      pwf        fp32 1x1 / Linear, Cin and Cout multiples of 32: the fp32 MFMA pointwise kernels (conv_f32_mfma.hip)
+      c32        bf16 32 -> 32 stride-1 'same' 3x3 / 1xk / kx1: the MFMA implicit-GEMM kernel
+      c32f       the same in fp32 (parity mode), k <= 13
+      wide33     bf16 32 -> 64 3x3 (MPViT stem[1]) as one launch per direction; WIDE_CONV = False leaves it to `slabs`
+      slabs      wider bf16 'same' convolutions (channel counts multiples of 32 up to 256, k <= 13) as 32x32 sub-GEMMs of the conv32 kernels: MPViT stem[1] and
+                 the wide CNN encoder of stc_tb / gtc_tb (32-64-96-128-256, nets/tcct.py:861-864)
+      slabs_f32  the same in fp32 (MPViT stem[1] 32->64 is a third of the parity mode's convolution time on the VALU kernel)
+      generic    everything else: the VALU convolution"""
+    if stride != 1 or Cin != Cin_w:
+        return 'generic'
+    if KH == 1 and KW == 1:
+        if padh != 0 or padw != 0 or Cin % 32 != 0:
+            return 'generic'
+        if in_dt == torch.bfloat16:
+            return 'pw'
+        return 'pwf' if in_dt == torch.float32 and out_dt == torch.float32 and Cout % 32 == 0 else 'generic'
+    if (in_dt != out_dt or in_dt not in (torch.bfloat16, torch.float32) or 2 * padh != KH - 1 or 2 * padw != KW - 1
+            or not (KH == 1 or KW == 1 or (KH == 3 and KW == 3))):
+        return 'generic'
+    bf = in_dt == torch.bfloat16
+    if Cin == 32 and Cout == 32:
+        if bf:
+            return 'c32'
+        return 'c32f' if max(KH, KW) <= 13 else 'generic'
+    if Cin % 32 != 0 or Cout % 32 != 0 or not (32 <= Cin <= 256 and 32 <= Cout <= 256) or max(KH, KW) > 13:
+        return 'generic'
+    if not bf:
+        return 'slabs_f32'
+    return 'wide33' if WIDE_CONV and Cin == 32 and Cout == 64 and KH == 3 and KW == 3 else 'slabs'
+
+
+def conv_fwd_route(route):
+    """the three directions take `route` = conv_route of the forward orientation (x's dtype in, the output's / dy's dtype out)"""
+    return 'generic' if route == 'pwf' and not F32_PW[0] else route
+
+
+def conv_dgrad_route(route, x_dt, dy_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
+    """the input gradient is the transposed convolution: dy -> dx with the roles of Cin and Cout swapped"""
+    if stride != 1 or Cin != Cin_w:
+        raise TcctError('conv2d dgrad: only stride-1 convs with unpadded channels need an input gradient')
+    if route == 'wide33':
+        return route
+    t = conv_route(dy_dt, x_dt, Cout, Cout, Cin, KH, KW, stride, padh, padw)
+    if (t == 'pw' and x_dt != torch.bfloat16) or (t == 'pwf' and not F32_PW[1]):
+        return 'generic'
+    return 'slabs' if t == 'wide33' else t          # 64 -> 32: the wide kernel only runs this way round as the gradient of 32 -> 64
+
+
+def conv_wgrad_route(route, x_dt, dy_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
+    if route == 'pwf' and not (F32_PW[2] and Cout <= 160):
+        route = 'generic'
+    if route == 'pw':
+        if dy_dt == torch.bfloat16 and Cout % 32 == 0:
+            # wider outputs (the qkv Linear of the factorised attention, Cout = 3 dim): slabs of <= 160 columns on the same kernel
+            return 'pw' if Cout <= 160 else 'pw_strided'
+        route = 'generic'
+    if (route == 'generic' and KH == 1 and KW == 1 and stride == 1 and Cout <= 8 and Cin == Cin_w and Cin <= 256
+            and (x_dt == torch.bfloat16 or dy_dt == torch.float32)):
+        return 'smalln'
+    return route
 
 
 def _wide_packs(w):
@@ -404,52 +433,22 @@ def _wide_packs(w):
     return buf
 
 
-def _mfma_slabs_f32_ok(in_dt, out_dt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-    """wider fp32 stride-1 'same' convolutions as 32x32 sub-GEMMs of the fp32 MFMA kernels (MPViT stem[1] 32->64 is a third of the parity mode's
-    convolution time on the VALU kernel; the wide CNN encoder of stc_tb / gtc_tb)"""
-    return (F32_MFMA and in_dt == torch.float32 and out_dt == torch.float32 and Cin == Cin_w and Cin % 32 == 0 and Cout % 32 == 0
-            and 32 <= Cin <= 256 and 32 <= Cout <= 256 and (Cin, Cout) != (32, 32) and stride == 1
-            and 2 * padh == KH - 1 and 2 * padw == KW - 1 and 1 < KH * KW <= 13 and (KH == 1 or KW == 1 or (KH == 3 and KW == 3)))
-
-
-def _conv_slabs_fwd_f32(x, w, bias, y, N, H, W, Cin, Cout, KH, KW, padh, padw, transposed):
-    """fp32 counterpart of _conv_slabs_fwd (no fused statistics): transposed=True computes the input gradient (x = dy, w OIHW [Cin here][Cout here])"""
-    for oh in range(Cout // 32):
-        for ih in range(Cin // 32):
-            wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.float32)
-            if not transposed:
-                lib.conv32f_pack_weights_sub(w, wp, KH, KW, 0, Cin, 32 * oh, 32 * ih)
-            else:
-                lib.conv32f_pack_weights_sub(w, wp, KH, KW, 1, Cout, 32 * ih, 32 * oh)
-            b = bias[32 * oh:32 * oh + 32] if (bias is not None and ih == 0) else None
-            lib.conv32f_fwd_strided(x, wp, b, y, N, H, W, KH, KW, padh, padw, Cin, 32 * ih, Cout, 32 * oh, 1 if ih > 0 else 0)
-
-
 def _conv_slabs_fwd(x, w, bias, y, N, H, W, Cin, Cout, KH, KW, padh, padw, transposed, stats=None, stat_pre=0):
-    """y[..., Cout] = conv(x[..., Cin]) via 32x32 sub-GEMMs; transposed=True computes the input gradient (x=dy, w OIHW [Cin_orig=Cout
-    here][...]) i.e. roles of the weight's O/I dims swap"""
-    wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.bfloat16)
+    """y[..., Cout] = conv(x[..., Cin]) via 32x32 sub-GEMMs of the conv32 kernels (bf16) / the fp32 MFMA kernels (no fused statistics there); transposed=True
+    computes the input gradient (x=dy, w OIHW [Cin_orig=Cout here][...]) i.e. roles of the weight's O/I dims swap"""
+    pack, fwd = (lib.conv32_pack_weights_sub, lib.conv32_fwd_strided) if x.dtype == torch.bfloat16 else (lib.conv32f_pack_weights_sub, lib.conv32f_fwd_strided)
     for oh in range(Cout // 32):
         for ih in range(Cin // 32):
+            wp = torch.empty(KH * KW * 1024, device=x.device, dtype=x.dtype)
             if not transposed:
-                lib.conv32_pack_weights_sub(w, wp, KH, KW, 0, Cin, 32 * oh, 32 * ih)
+                pack(w, wp, KH, KW, 0, Cin, 32 * oh, 32 * ih)
             else:       # w is OIHW [Cin(this call's input = orig Cout)][Cout(this call's output = orig Cin)]
-                lib.conv32_pack_weights_sub(w, wp, KH, KW, 1, Cout, 32 * ih, 32 * oh)
+                pack(w, wp, KH, KW, 1, Cout, 32 * ih, 32 * oh)
             b = bias[32 * oh:32 * oh + 32] if (bias is not None and ih == 0) else None
             if stats is not None and ih == Cin // 32 - 1:       # the last input slab: the accumulated output is what the BatchNorm statistics count
                 lib.conv32_fwd_strided_bnstats(x, wp, b, y, N, H, W, KH, KW, padh, padw, Cin, 32 * ih, Cout, 32 * oh, 1 if ih > 0 else 0, stats, stat_pre)
             else:
-                lib.conv32_fwd_strided(x, wp, b, y, N, H, W, KH, KW, padh, padw, Cin, 32 * ih, Cout, 32 * oh, 1 if ih > 0 else 0)
-            if ih + 1 < Cin // 32 or oh + 1 < Cout // 32:
-                wp = torch.empty_like(wp)
-
-
-# Fused 3x3 conv32 backward (tcct_conv32_bwd3x3): correct and tested, but OFF by default -- alone it takes 0.49 ms against 0.23 + 0.31 ms for
-# the separate input-gradient / weight-gradient kernels at level 0, and inside the step it gains nothing (29.3 vs 29.3 ms, same box): the
-# separate weight gradient runs on the side stream beside the input-gradient chain, the fused kernel sits on the critical path and is
-# bound by the latency of its one 8-wave block per CU (111 KB of LDS), not by HBM.  `bench.py --set FUSED_CONV_BWD=1` enables it.
-FUSED_CONV_BWD = False
-FUSED_PW_BWD = True        # False: separate input-gradient / weight-gradient kernels (A/B timing)
+                fwd(x, wp, b, y, N, H, W, KH, KW, padh, padw, Cin, 32 * ih, Cout, 32 * oh, 1 if ih > 0 else 0)
 
 
 def _pw_bwd_ok(x, dy, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
@@ -459,10 +458,207 @@ def _pw_bwd_ok(x, dy, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
             and x.numel() * 2 < 2 ** 31 and dy.numel() * 2 < 2 ** 31)
 
 
-def _pw_ok(in_dt, Cin, Cin_w, KH, KW, stride, padh, padw):
-    """the MFMA pointwise kernels cover bf16 1x1 convs / Linear with Cin % 32 == 0"""
-    return (in_dt == torch.bfloat16 and KH == 1 and KW == 1 and stride == 1 and padh == 0 and padw == 0 and Cin == Cin_w
-            and Cin % 32 == 0)
+def _packs32(w, KH, KW, need_t):
+    """(forward pack, input-gradient pack or None) of a 32 -> 32 weight: this step's pack-all launch (begin_step), or packed here -- with need_t both packs
+    out of one launch"""
+    cached = _pack_lookup(w, KH, KW)
+    if cached is not None:
+        return cached
+    n = KH * KW * 1024
+    if need_t:
+        wp2 = torch.empty(2 * n, device=w.device, dtype=torch.bfloat16)
+        lib.conv32_pack_weights_both(w, wp2, KH, KW)
+        return wp2[:n], wp2[n:]
+    wp = torch.empty(n, device=w.device, dtype=torch.bfloat16)
+    lib.conv32_pack_weights(w, wp, KH, KW, 0)
+    return wp, None
+
+
+def _pack_t(wp_t, w, KH, KW):
+    """the input-gradient pack the forward left behind, or packed here"""
+    if wp_t is None:
+        wp_t = torch.empty(KH * KW * 1024, device=w.device, dtype=torch.bfloat16)
+        lib.conv32_pack_weights(w, wp_t, KH, KW, 1)
+    return wp_t
+
+
+# ---- the launchers of every route: forward(ctx, x, w, bias, y, stats_box, g), input gradient(ctx, dy, w, dskip, dx, g) -> the dskip still to be added (None
+# when the kernel's epilogue took it), weight gradient(x, dy, dw, db, g); g = (N, H, W, Cin, Cin_w, Cout, KH, KW, stride, padh, padw) of the FORWARD
+def _stat_sums(stats_box, C, device):
+    """pre-zeroed [sum | sum of squares] of the consumer's train-mode BatchNorm (stats_box = [pre_act_code, None]), or None"""
+    if stats_box is None:
+        return None, 0
+    stats_box[1] = _zeros((2 * C,), torch.float64, device)
+    return stats_box[1], stats_box[0]
+
+
+def _clear_unless_prezeroed(dw, db):
+    """in front of kernels that accumulate into dw / db: inside a pooled step the gradient slots and the pool are already zero"""
+    if not ZERO.active:
+        dw.zero_()
+        if db is not None:
+            db.zero_()
+
+
+def _fwd_pw(ctx, x, w, bias, y, stats_box, g):
+    N, H, W, Cin, _, Cout = g[:6]
+    if stats_box is not None and y.dtype == torch.bfloat16 and Cout % 32 == 0 and Cout <= 160:
+        sums, pre = _stat_sums(stats_box, Cout, x.device)
+        lib.pw_fwd_bnstats(x, w, bias, y, N * H * W, Cin, Cout, sums, pre)
+    else:
+        lib.pw_fwd(x, w, bias, y, N * H * W, Cin, Cout, 0, dtype_code(y.dtype))
+
+
+def _dgrad_pw(ctx, dy, w, dskip, dx, g):
+    N, H, W, Cin, _, Cout = g[:6]
+    if dskip is not None and Cin % 32 == 0:
+        lib.pw_dgrad_residual(dy, w, dskip, dx, None, N * H * W, Cout, Cin)
+        return None
+    lib.pw_fwd(dy, w, None, dx, N * H * W, Cout, Cin, 1, dtype_code(dx.dtype))
+    return dskip
+
+
+def _wgrad_pw(x, dy, dw, db, g):
+    N, H, W, Cin, _, Cout = g[:6]
+    (lib.pw_wgrad if x.dtype == torch.bfloat16 else lib.pwf_wgrad)(x, dy, dw, db, N * H * W, Cin, Cout)
+
+
+def _wgrad_pw_strided(x, dy, dw, db, g):
+    N, H, W, Cin, _, Cout = g[:6]
+    dy2, dw2 = dy.view(-1, Cout), dw.view(Cout, Cin)
+    for c0 in range(0, Cout, 160):
+        n = min(160, Cout - c0)
+        lib.pw_wgrad_strided(x, dy2[0, c0:], Cout, dw2[c0:], db[c0:] if db is not None else None, N * H * W, Cin, n)
+
+
+def _wgrad_smalln(x, dy, dw, db, g):
+    N, H, W, Cin, _, Cout = g[:6]
+    lib.pw_wgrad_smalln(x, dy, dw, db, N * H * W, Cin, Cout, dtype_code(x.dtype), dtype_code(dy.dtype))
+
+
+def _fwd_pwf(ctx, x, w, bias, y, stats_box, g):
+    N, H, W, Cin, _, Cout = g[:6]
+    lib.pwf_fwd(x, w, bias, y, N * H * W, Cin, Cout, 0)
+
+
+def _dgrad_pwf(ctx, dy, w, dskip, dx, g):
+    N, H, W, Cin, _, Cout = g[:6]
+    lib.pwf_fwd(dy, w, None, dx, N * H * W, Cout, Cin, 1)
+    return dskip
+
+
+def _fwd_wide33(ctx, x, w, bias, y, stats_box, g):
+    N, H, W = g[:3]
+    sums, pre = _stat_sums(stats_box, 64, x.device)
+    ctx.wp_wide = _wide_packs(w)
+    lib.conv32x64_fwd33(x, ctx.wp_wide, 2 * 9 * 1024, bias, y, N, H, W, sums, pre, 0)
+
+
+def _dgrad_wide33(ctx, dy, w, dskip, dx, g):
+    N, H, W = g[:3]
+    lib.conv64x32_dgrad33(dy, ctx.wp_wide[9 * 1024:], 2 * 9 * 1024, dx, N, H, W, 0)      # the packs the forward of this route left behind
+    return dskip
+
+
+def _wgrad_wide33(x, dy, dw, db, g):
+    N, H, W = g[:3]
+    _clear_unless_prezeroed(dw, db)
+    lib.conv32x64_wgrad33(x, dy, dw, db, N, H, W, 0)
+
+
+def _fwd_slabs(ctx, x, w, bias, y, stats_box, g):
+    N, H, W, Cin, _, Cout, KH, KW, _, padh, padw = g
+    sums, pre = _stat_sums(stats_box if x.dtype == torch.bfloat16 else None, Cout, x.device)
+    _conv_slabs_fwd(x, w, bias, y, N, H, W, Cin, Cout, KH, KW, padh, padw, False, sums, pre)
+
+
+def _dgrad_slabs(ctx, dy, w, dskip, dx, g):
+    N, H, W, Cin, _, Cout, KH, KW, _, padh, padw = g
+    _conv_slabs_fwd(dy, w, None, dx, N, H, W, Cout, Cin, KH, KW, KH - 1 - padh, KW - 1 - padw, True)
+    return dskip
+
+
+def _wgrad_slabs(x, dy, dw, db, g):
+    N, H, W, Cin, _, Cout, KH, KW, _, padh, padw = g
+    wgrad_strided = lib.conv32_wgrad_strided if x.dtype == torch.bfloat16 else lib.conv32f_wgrad_strided
+    _clear_unless_prezeroed(dw, db)
+    for oh in range(Cout // 32):
+        for ih in range(Cin // 32):
+            wgrad_strided(x, dy, dw, db if ih == 0 else None, N, H, W, KH, KW, padh, padw, Cin, 32 * ih, Cout, 32 * oh, Cin, 32 * oh, 32 * ih)
+
+
+def _fwd_c32(ctx, x, w, bias, y, stats_box, g):
+    N, H, W, _, _, _, KH, KW, _, padh, padw = g
+    wp, ctx.wp_t = _packs32(w, KH, KW, ctx.needs_input_grad[0])
+    if stats_box is not None:
+        sums, pre = _stat_sums(stats_box, 32, x.device)
+        lib.conv32_fwd_bnstats(x, wp, bias, y, N, H, W, KH, KW, padh, padw, sums, pre)
+    else:
+        lib.conv32_fwd(x, wp, bias, y, N, H, W, KH, KW, padh, padw)
+
+
+def _dgrad_c32(ctx, dy, w, dskip, dx, g):
+    N, H, W, _, _, _, KH, KW, _, padh, padw = g
+    wp = _pack_t(ctx.wp_t, w, KH, KW)
+    if dskip is not None:
+        lib.conv32_fwd_add(dy, wp, None, dskip, dx, N, H, W, KH, KW, KH - 1 - padh, KW - 1 - padw)
+    else:
+        lib.conv32_fwd(dy, wp, None, dx, N, H, W, KH, KW, KH - 1 - padh, KW - 1 - padw)
+    return None
+
+
+def _wgrad_c32(x, dy, dw, db, g):
+    N, H, W, _, _, _, KH, KW, _, padh, padw = g
+    (lib.conv32_wgrad if x.dtype == torch.bfloat16 else lib.conv32f_wgrad)(x, dy, dw, db, N, H, W, KH, KW, padh, padw)
+
+
+def _fwd_c32f(ctx, x, w, bias, y, stats_box, g):
+    N, H, W, _, _, _, KH, KW, _, padh, padw = g
+    wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.float32)
+    lib.conv32f_pack_weights(w, wp, KH, KW, 0)
+    lib.conv32f_fwd(x, wp, bias, None, y, N, H, W, KH, KW, padh, padw)
+
+
+def _dgrad_c32f(ctx, dy, w, dskip, dx, g):
+    N, H, W, _, _, _, KH, KW, _, padh, padw = g
+    wp = torch.empty(KH * KW * 1024, device=dy.device, dtype=torch.float32)
+    lib.conv32f_pack_weights(w, wp, KH, KW, 1)
+    lib.conv32f_fwd(dy, wp, None, dskip, dx, N, H, W, KH, KW, KH - 1 - padh, KW - 1 - padw)
+    return None
+
+
+def _fwd_generic(ctx, x, w, bias, y, stats_box, g):
+    lib.conv2d_fwd(x, w, bias, y, *g, dtype_code(x.dtype), dtype_code(y.dtype))
+
+
+def _dgrad_generic(ctx, dy, w, dskip, dx, g):
+    N, H, W, Cin, _, Cout, KH, KW, _, padh, padw = g
+    lib.conv2d_dgrad(dy, w, dx, N, H, W, Cin, Cout, KH, KW, padh, padw, dtype_code(dy.dtype), dtype_code(dx.dtype))
+    return dskip
+
+
+def _wgrad_generic(x, dy, dw, db, g):
+    lib.conv2d_wgrad(x, dy, dw, db, *g, dtype_code(x.dtype), dtype_code(dy.dtype))
+
+
+# route -> (forward, input gradient, weight gradient); `pw_strided` and `smalln` only exist as weight gradients (conv_wgrad_route)
+_CONV_ROUTES = {
+    'pw': (_fwd_pw, _dgrad_pw, _wgrad_pw),
+    'pwf': (_fwd_pwf, _dgrad_pwf, _wgrad_pw),
+    'wide33': (_fwd_wide33, _dgrad_wide33, _wgrad_wide33),
+    'slabs': (_fwd_slabs, _dgrad_slabs, _wgrad_slabs),
+    'slabs_f32': (_fwd_slabs, _dgrad_slabs, _wgrad_slabs),            # the same loops: the slab helpers pick the kernels by dtype
+    'c32': (_fwd_c32, _dgrad_c32, _wgrad_c32),
+    'c32f': (_fwd_c32f, _dgrad_c32f, _wgrad_c32),
+    'generic': (_fwd_generic, _dgrad_generic, _wgrad_generic),
+    'pw_strided': (None, None, _wgrad_pw_strided),
+    'smalln': (None, None, _wgrad_smalln),
+}
+
+
+def _param_of(w):
+    """the parameter behind a weight: w may be a view of the nn.Linear weight (conv2d wrapper) -> gradient destinations look through ._base"""
+    return w if hasattr(w, '_grad_slot') or w._base is None else w._base
 
 
 class _Conv2d(_FastFunction):
@@ -478,190 +674,50 @@ class _Conv2d(_FastFunction):
         Wo = (W + 2 * padw - KW) // stride + 1
         odt = out_dtype or x.dtype
         y = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=odt)
-        mfma = _mfma32_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw)
-        if _pw_ok(x.dtype, Cin, Cin_w, KH, KW, stride, padh, padw) and not mfma:
-            if stats_box is not None and odt == torch.bfloat16 and Cout % 32 == 0 and Cout <= 160:
-                sums = ZERO.get((2 * Cout,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * Cout, device=x.device, dtype=torch.float64)
-                lib.pw_fwd_bnstats(x, w, bias, y, N * H * W, Cin, Cout, sums, stats_box[0])
-                stats_box[1] = sums
-            else:
-                lib.pw_fwd(x, w, bias, y, N * H * W, Cin, Cout, 0, dtype_code(odt))
-        elif _wide33_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-            sums = None
-            if stats_box is not None:       # fused train-mode BN statistics of the consumer
-                sums = ZERO.get((2 * Cout,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * Cout, device=x.device, dtype=torch.float64)
-                stats_box[1] = sums
-            ctx.wp_wide = _wide_packs(w)
-            lib.conv32x64_fwd33(x, ctx.wp_wide, 2 * 9 * 1024, bias, y, N, H, W, sums, stats_box[0] if stats_box is not None else 0, 0)
-        elif _mfma_slabs_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-            sums = None
-            if stats_box is not None:       # fused train-mode BN statistics of the consumer (MPViT stem[1])
-                sums = ZERO.get((2 * Cout,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * Cout, device=x.device, dtype=torch.float64)
-                stats_box[1] = sums
-            _conv_slabs_fwd(x, w, bias, y, N, H, W, Cin, Cout, KH, KW, padh, padw, False, sums, stats_box[0] if stats_box is not None else 0)
-        elif mfma:
-            cached = _pack_lookup(w, KH, KW)
-            if cached is not None:          # made by this step's single pack launch (begin_step)
-                wp, ctx.wp_t = cached
-            elif ctx.needs_input_grad[0]:   # the input-gradient pack of the same weights comes out of the same launch (used by backward())
-                wp2 = torch.empty(2 * KH * KW * 1024, device=x.device, dtype=torch.bfloat16)
-                lib.conv32_pack_weights_both(w, wp2, KH, KW)
-                wp, ctx.wp_t = wp2[:KH * KW * 1024], wp2[KH * KW * 1024:]
-            else:
-                wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.bfloat16)
-                lib.conv32_pack_weights(w, wp, KH, KW, 0)
-            if stats_box is not None:       # fused train-mode BN statistics of the consumer (stats_box = [pre_act_code, None])
-                sums = ZERO.get((64,), torch.float64, x.device) if ZERO.active else torch.zeros(64, device=x.device, dtype=torch.float64)
-                lib.conv32_fwd_bnstats(x, wp, bias, y, N, H, W, KH, KW, padh, padw, sums, stats_box[0])
-                stats_box[1] = sums
-            else:
-                lib.conv32_fwd(x, wp, bias, y, N, H, W, KH, KW, padh, padw)
-        elif _mfma32f_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-            wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.float32)
-            lib.conv32f_pack_weights(w, wp, KH, KW, 0)
-            lib.conv32f_fwd(x, wp, bias, None, y, N, H, W, KH, KW, padh, padw)
-        elif _mfma_slabs_f32_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-            _conv_slabs_fwd_f32(x, w, bias, y, N, H, W, Cin, Cout, KH, KW, padh, padw, False)
-        elif F32_PW[0] and _pwf_ok(x.dtype, odt, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-            lib.pwf_fwd(x, w, bias, y, N * H * W, Cin, Cout, 0)
-        else:
-            lib.conv2d_fwd(x, w, bias, y, N, H, W, Cin, Cin_w, Cout, KH, KW, stride, padh, padw, dtype_code(x.dtype),
-                           dtype_code(odt))
+        shape = (Cin, Cin_w, Cout, KH, KW, stride, padh, padw)
+        ctx.route = conv_route(x.dtype, odt, *shape)            # classified once: backward() resolves its two directions from it
+        ctx.geom = (N, H, W) + shape
+        _CONV_ROUTES[conv_fwd_route(ctx.route)][0](ctx, x, w, bias, y, stats_box, ctx.geom)
         ctx.save_for_backward(x, w)
-        ctx.cfg = (stride, padh, padw, bias is not None)
-        # gradient destinations: w may be a view of the nn.Linear weight (conv2d wrapper) -> look through ._base
-        wsrc = w if hasattr(w, '_grad_slot') or w._base is None else w._base
-        ctx.params = (wsrc, bias)
+        ctx.params = (_param_of(w), bias)
         return (y, x.view_as(x)) if fork else y
 
     @staticmethod
     def backward(ctx, dy, dskip=None):
         x, w = ctx.saved_tensors
-        stride, padh, padw, has_bias = ctx.cfg
         wsrc, bsrc = ctx.params
         if dy is None:          # only the alias was used downstream
             return dskip, None, None, None, None, None, None, None, None
         dy = _c(dy)
         if dskip is not None:
             dskip = _as(dskip, x.dtype)
-        N, H, W, Cin = x.shape
-        Cout, Cin_w, KH, KW = w.shape
+        g = ctx.geom
+        N, H, W = g[:3]
+        shape = Cin, Cin_w, Cout, KH, KW, stride, padh, padw = g[3:]
         dx = dw = db = None
-        if (FUSED_PW_BWD and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _pw_bwd_ok(x, dy, Cin, Cin_w, Cout, KH, KW, stride, padh, padw)
-                and (dskip is None or dskip.shape == x.shape)):
+        if (ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _pw_bwd_ok(x, dy, *shape) and (dskip is None or dskip.shape == x.shape)):
             # 1x1 convolution: input gradient, weight gradient and bias gradient in ONE pass over dy (tcct_pw_bwd); a second
             # consumer's gradient of x (fork) rides on the dx epilogue
             dx = torch.empty_like(x)
             dw = _grad_out(wsrc, tuple(w.shape))
-            db = _grad_out(bsrc) if has_bias else None
+            db = _grad_out(bsrc) if bsrc is not None else None
             lib.pw_bwd(x, dy, w, dskip, dx, dw, db, N * H * W, Cin, Cout)
             return dx, _ret(dw, wsrc), _ret(db, bsrc), None, None, None, None, None, None
-        if (FUSED_CONV_BWD and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and KH == 3 and KW == 3 and dy.dtype == torch.bfloat16
-                and _mfma32_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw) and H * W * 64 < 2 ** 31):
-            # dense 3x3 32->32: input gradient (+ a second consumer's gradient) and weight / bias gradient from ONE staging of dy
-            wp = getattr(ctx, 'wp_t', None)
-            if wp is None:
-                wp = torch.empty(9 * 1024, device=x.device, dtype=torch.bfloat16)
-                lib.conv32_pack_weights(w, wp, 3, 3, 1)
-            dx = torch.empty_like(x)
-            dw = _grad_out(wsrc, tuple(w.shape))
-            db = _grad_out(bsrc) if has_bias else None
-            lib.conv32_bwd3x3(x, dy, wp, dskip, dx, dw, db, N, H, W)
-            return dx, _ret(dw, wsrc), _ret(db, bsrc), None, None, None, None, None, None
         if ctx.needs_input_grad[0]:
-            if stride != 1 or Cin != Cin_w:
-                raise TcctError('conv2d dgrad: only stride-1 convs with unpadded channels need an input gradient')
+            route = conv_dgrad_route(ctx.route, x.dtype, dy.dtype, *shape)
             dx = torch.empty_like(x)
-            if (_pw_ok(dy.dtype, Cout, Cout, KH, KW, stride, padh, padw) and x.dtype == torch.bfloat16
-                    and not _mfma32_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw)):
-                if dskip is not None and Cin % 32 == 0:
-                    lib.pw_dgrad_residual(dy, w, dskip, dx, None, N * H * W, Cout, Cin)
-                    dskip = None
-                else:
-                    lib.pw_fwd(dy, w, None, dx, N * H * W, Cout, Cin, 1, dtype_code(x.dtype))
-            elif _wide33_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-                buf = getattr(ctx, 'wp_wide', None)
-                if buf is None:
-                    buf = _wide_packs(w)
-                lib.conv64x32_dgrad33(dy, buf[9 * 1024:], 2 * 9 * 1024, dx, N, H, W, 0)          # (a second consumer's gradient: the explicit pass below)
-            elif _mfma_slabs_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw):
-                _conv_slabs_fwd(dy, w, None, dx, N, H, W, Cout, Cin, KH, KW, KH - 1 - padh, KW - 1 - padw, True)
-            elif _mfma32_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw):
-                wp = getattr(ctx, 'wp_t', None)
-                if wp is None:
-                    wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.bfloat16)
-                    lib.conv32_pack_weights(w, wp, KH, KW, 1)
-                if dskip is not None:
-                    lib.conv32_fwd_add(dy, wp, None, dskip, dx, N, H, W, KH, KW, KH - 1 - padh, KW - 1 - padw)
-                    dskip = None
-                else:
-                    lib.conv32_fwd(dy, wp, None, dx, N, H, W, KH, KW, KH - 1 - padh, KW - 1 - padw)
-            elif _mfma_slabs_f32_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw):
-                _conv_slabs_fwd_f32(dy, w, None, dx, N, H, W, Cout, Cin, KH, KW, KH - 1 - padh, KW - 1 - padw, True)
-            elif F32_PW[1] and _pwf_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw):
-                lib.pwf_fwd(dy, w, None, dx, N * H * W, Cout, Cin, 1)
-            elif _mfma32f_ok(dy.dtype, x.dtype, Cout, Cout, Cin, KH, KW, stride, padh, padw):
-                wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.float32)
-                lib.conv32f_pack_weights(w, wp, KH, KW, 1)
-                lib.conv32f_fwd(dy, wp, None, dskip, dx, N, H, W, KH, KW, KH - 1 - padh, KW - 1 - padw)
-                dskip = None
-            else:
-                lib.conv2d_dgrad(dy, w, dx, N, H, W, Cin, Cout, KH, KW, padh, padw, dtype_code(dy.dtype), dtype_code(x.dtype))
+            dskip = _CONV_ROUTES[route][1](ctx, dy, w, dskip, dx, g)
             if dskip is not None:       # kernels without the fused epilogue: one explicit pass
                 tot = torch.empty_like(dx)
                 lib.add(dx, dskip, tot, tot.numel(), dtype_code(tot.dtype))
                 dx = tot
         elif dskip is not None:
             dx = dskip
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            with _wgrad_stream(_slot_written(wsrc, bsrc if has_bias else None), x, dy):
+        if ctx.needs_input_grad[1] or (bsrc is not None and ctx.needs_input_grad[2]):
+            with _wgrad_stream(_slot_written(wsrc, bsrc), x, dy):
                 dw = _grad_out(wsrc, tuple(w.shape))
-                db = _grad_out(bsrc) if has_bias else None
-                if _mfma32_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-                    lib.conv32_wgrad(x, dy, dw, db, N, H, W, KH, KW, padh, padw)
-                elif _mfma32f_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-                    lib.conv32f_wgrad(x, dy, dw, db, N, H, W, KH, KW, padh, padw)
-                elif _mfma_slabs_f32_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-                    if not ZERO.active:
-                        dw.zero_()
-                        if db is not None:
-                            db.zero_()
-                    for oh in range(Cout // 32):
-                        for ih in range(Cin // 32):
-                            lib.conv32f_wgrad_strided(x, dy, dw, db if ih == 0 else None, N, H, W, KH, KW, padh, padw, Cin, 32 * ih, Cout, 32 * oh,
-                                                      Cin, 32 * oh, 32 * ih)
-                elif F32_PW[2] and _pwf_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw) and Cout <= 160:
-                    lib.pwf_wgrad(x, dy, dw, db, N * H * W, Cin, Cout)
-                elif _wide33_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-                    if not ZERO.active:
-                        dw.zero_()
-                        if db is not None:
-                            db.zero_()
-                    lib.conv32x64_wgrad33(x, dy, dw, db, N, H, W, 0)
-                elif _mfma_slabs_ok(x.dtype, dy.dtype, Cin, Cin_w, Cout, KH, KW, stride, padh, padw):
-                    if not ZERO.active:
-                        dw.zero_()
-                        if db is not None:
-                            db.zero_()
-                    for oh in range(Cout // 32):
-                        for ih in range(Cin // 32):
-                            lib.conv32_wgrad_strided(x, dy, dw, db if ih == 0 else None, N, H, W, KH, KW, padh, padw, Cin, 32 * ih, Cout,
-                                                     32 * oh, Cin, 32 * oh, 32 * ih)
-                elif (_pw_ok(x.dtype, Cin, Cin_w, KH, KW, stride, padh, padw) and dy.dtype == torch.bfloat16 and Cout % 32 == 0
-                      and Cout <= 160):
-                    lib.pw_wgrad(x, dy, dw, db, N * H * W, Cin, Cout)
-                elif _pw_ok(x.dtype, Cin, Cin_w, KH, KW, stride, padh, padw) and dy.dtype == torch.bfloat16 and Cout % 32 == 0:
-                    # wider outputs (the qkv Linear of the factorised attention, Cout = 3 dim): slabs of <= 160 columns on the same kernel
-                    dy2, dw2 = dy.view(-1, Cout), dw.view(Cout, Cin)
-                    for c0 in range(0, Cout, 160):
-                        n = min(160, Cout - c0)
-                        lib.pw_wgrad_strided(x, dy2[0, c0:], Cout, dw2[c0:], db[c0:] if db is not None else None, N * H * W, Cin, n)
-                elif KH == 1 and KW == 1 and stride == 1 and Cout <= 8 and Cin == Cin_w and Cin <= 256 and (
-                        x.dtype == torch.bfloat16 or dy.dtype == torch.float32):
-                    lib.pw_wgrad_smalln(x, dy, dw, db, N * H * W, Cin, Cout, dtype_code(x.dtype), dtype_code(dy.dtype))
-                else:
-                    lib.conv2d_wgrad(x, dy, dw, db, N, H, W, Cin, Cin_w, Cout, KH, KW, stride, padh, padw, dtype_code(x.dtype),
-                                     dtype_code(dy.dtype))
+                db = _grad_out(bsrc) if bsrc is not None else None
+                _CONV_ROUTES[conv_wgrad_route(ctx.route, x.dtype, dy.dtype, *shape)][2](x, dy, dw, db, g)
         return dx, _ret(dw, wsrc), _ret(db, bsrc), None, None, None, None, None, None
 
 
@@ -713,20 +769,6 @@ def conv3x3_chain_ok(x, w1, b1, w2, b2, stride1, pad1, stride2, pad2):
             and x.shape[0] * x.shape[1] * x.shape[2] >= CHAIN_MIN_PIXELS)
 
 
-def _packs33(ctx_w, need_t):
-    """(forward pack, input-gradient pack or None) of a 3x3 32 -> 32 weight: this step's pack-all launch, or packed here"""
-    cached = _pack_lookup(ctx_w, 3, 3)
-    if cached is not None:
-        return cached
-    if need_t:
-        wp2 = torch.empty(2 * 9 * 1024, device=ctx_w.device, dtype=torch.bfloat16)
-        lib.conv32_pack_weights_both(ctx_w, wp2, 3, 3)
-        return wp2[:9 * 1024], wp2[9 * 1024:]
-    wp = torch.empty(9 * 1024, device=ctx_w.device, dtype=torch.bfloat16)
-    lib.conv32_pack_weights(ctx_w, wp, 3, 3, 0)
-    return wp, None
-
-
 class _ConvChain33(_FastFunction):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, stats_box, fork):
@@ -735,11 +777,11 @@ class _ConvChain33(_FastFunction):
         N, H, W, _ = x.shape
         mid, y = torch.empty_like(x), torch.empty_like(x)
         need_t = ctx.needs_input_grad[0]
-        wp1, ctx.wp_t1 = _packs33(w1, need_t)
-        wp2, ctx.wp_t2 = _packs33(w2, True)             # d mid is always needed: it is the dy operand of the first convolution's weight gradient
+        wp1, ctx.wp_t1 = _packs32(w1, 3, 3, need_t)
+        wp2, ctx.wp_t2 = _packs32(w2, 3, 3, True)             # d mid is always needed: it is the dy operand of the first convolution's weight gradient
         sums = None
         if stats_box is not None:
-            sums = ZERO.get((64,), torch.float64, x.device) if ZERO.active else torch.zeros(64, device=x.device, dtype=torch.float64)
+            sums = _zeros((64,), torch.float64, x.device)
             stats_box[1] = sums
         lib.conv32_chain33(x, wp1, b1, mid, wp2, b2, y, None, N, H, W, sums)
         ctx.save_for_backward(x, mid, w1, w2)
@@ -761,16 +803,10 @@ class _ConvChain33(_FastFunction):
         need_mid = nx or g1             # d mid feeds the input-gradient chain and the first convolution's weight gradient
         dx = dmid = None
         if need_mid:
-            wt2 = ctx.wp_t2
-            if wt2 is None:
-                wt2 = torch.empty(9 * 1024, device=x.device, dtype=torch.bfloat16)
-                lib.conv32_pack_weights(w2, wt2, 3, 3, 1)
+            wt2 = _pack_t(ctx.wp_t2, w2, 3, 3)
             dmid = torch.empty_like(x) if g1 else None          # nobody reads d mid when the first convolution is frozen: the chain does not store it
             if nx:
-                wt1 = ctx.wp_t1
-                if wt1 is None:
-                    wt1 = torch.empty(9 * 1024, device=x.device, dtype=torch.bfloat16)
-                    lib.conv32_pack_weights(w1, wt1, 3, 3, 1)
+                wt1 = _pack_t(ctx.wp_t1, w1, 3, 3)
                 dx = torch.empty_like(x)
                 lib.conv32_chain33(dy, wt2, None, dmid, wt1, None, dx, _as(dskip, x.dtype) if dskip is not None else None, N, H, W, None)
             else:
@@ -877,24 +913,17 @@ def run_parallel(tag, fa, fb):
     """(fa(), fb()) with fb issued on the side stream `tag` and joined before returning"""
     if not (PARALLEL_BRANCHES and torch.cuda.is_available()):
         return fa(), fb()
-    cur = torch.cuda.current_stream()
-    side = _SIDE_STREAMS.get((tag, cur.device.index))
-    if side is None:
-        side = _SIDE_STREAMS[(tag, cur.device.index)] = fresh_stream(cur.device)
+    cur, side = torch.cuda.current_stream(), side_stream(tag)
     side.wait_stream(cur)
     with torch.cuda.stream(side):
         rb = fb()
     ra = fa()
     cur.wait_stream(side)
-    if ZERO.active:
-        # inside a pooled training step: keep what was allocated on the side stream and is consumed on the current one alive until end_step() instead of
-        # record_stream()ing it -- every later piece of side-stream work starts behind a `side.wait_stream(cur)`, i.e. behind the readers, so a block freed after
-        # the step's end cannot be overwritten early; record_stream() parks a freed block until the host-side event query sees the GPU catch up, and with the
-        # host a third of a step ahead the reserved pool grew by 0.4 GB per step (tests/test_fullsize_gpu.py::test_allocator_pool_stays_bounded_over_steps_fullsize)
-        _WGRAD_KEEP.extend(_tensors(rb))
-    else:
-        for t in _tensors(rb):
-            t.record_stream(cur)        # allocated on the side stream, consumed on the current one
+    # inside a pooled training step: keep what was allocated on the side stream and is consumed on the current one alive until end_step() instead of
+    # record_stream()ing it -- every later piece of side-stream work starts behind a `side.wait_stream(cur)`, i.e. behind the readers, so a block freed after
+    # the step's end cannot be overwritten early; record_stream() parks a freed block until the host-side event query sees the GPU catch up, and with the
+    # host a third of a step ahead the reserved pool grew by 0.4 GB per step (tests/test_fullsize_gpu.py::test_allocator_pool_stays_bounded_over_steps_fullsize)
+    keep_until_end_of_step(*_tensors(rb), cur)
     return ra, rb
 
 
@@ -930,10 +959,7 @@ def run_interleaved(tag, ga, gb, outs_b):
         for _ in ga:
             pass
         return
-    cur = torch.cuda.current_stream()
-    side = _SIDE_STREAMS.get((tag, cur.device.index))
-    if side is None:
-        side = _SIDE_STREAMS[(tag, cur.device.index)] = fresh_stream(cur.device)
+    cur, side = torch.cuda.current_stream(), side_stream(tag)
     side.wait_stream(cur)
     done_a = done_b = False
     end = object()
@@ -966,16 +992,16 @@ def conv_bn_act(x, w, bias=None, stride=1, pad=0, bn=None, pre_act=None, post_ac
     N, H, W, Cin = x4.shape
     Cout, Cin_w, KH, KW = w4.shape
     pre, post = ACT[pre_act], ACT[post_act]
-    mfma = _mfma32_ok(x4.dtype, x4.dtype, Cin, Cin_w, Cout, KH, KW, stride, ph, pw)
-    pwk = _pw_ok(x4.dtype, Cin, Cin_w, KH, KW, stride, ph, pw) and not mfma and (bn is not None or pre != 0 or post != 0)
-    if (not (mfma or pwk) and bn is not None and Cin == 32 and Cin_w == 32 and _mfma_slabs_ok(x4.dtype, x4.dtype, Cin, Cin_w, Cout, KH, KW, stride, ph, pw)):
+    route = conv_route(x4.dtype, x4.dtype, Cin, Cin_w, Cout, KH, KW, stride, ph, pw)
+    mfma = route == 'c32'
+    pwk = route == 'pw' and (bn is not None or pre != 0 or post != 0)
+    if bn is not None and Cin == 32 and route in ('slabs', 'wide33'):
         # round 6: a wider convolution with ONE input slab (MPViT stem[1], 32 -> 64): every 32-channel output slab with its part of the eval-mode BatchNorm + activations
         # in the epilogue (no separate normalisation pass over the 64-channel tensor)
         y = torch.empty((N, H, W, Cout), device=x.device, dtype=x.dtype)
         for oh in range(Cout // 32):
             sl = slice(32 * oh, 32 * oh + 32)
-            ab = torch.empty(64, device=x.device, dtype=torch.float32)
-            lib.bn_eval_ab(32, bn[0][sl], bn[1][sl], float(bn[4]), bn[2][sl], bn[3][sl], torch.empty(64, device=x.device, dtype=torch.float32), ab)
+            ab = _eval_ab(bn, 32, x.device, sl)
             wp = torch.empty(KH * KW * 1024, device=x.device, dtype=torch.bfloat16)
             lib.conv32_pack_weights_sub(w4, wp, KH, KW, 0, Cin, 32 * oh, 0)
             lib.conv32_fwd_strided_affine(x4, wp, bias[sl] if bias is not None else None, y, N, H, W, KH, KW, ph, pw, Cin, 0, Cout, 32 * oh, ab, pre, post)
@@ -987,10 +1013,7 @@ def conv_bn_act(x, w, bias=None, stride=1, pad=0, bn=None, pre_act=None, post_ac
         if pre != 0:
             y = act(y, pre_act)
         return act(y, post_act) if post != 0 else y
-    ab = None
-    if bn is not None:
-        ab = torch.empty(2 * Cout, device=x.device, dtype=torch.float32)
-        lib.bn_eval_ab(Cout, bn[0], bn[1], float(bn[4]), bn[2], bn[3], torch.empty(2 * Cout, device=x.device, dtype=torch.float32), ab)
+    ab = _eval_ab(bn, Cout, x.device) if bn is not None else None
     y = torch.empty((N, H, W, Cout), device=x.device, dtype=x.dtype)
     if pwk:
         lib.pw_fwd_affine(x4, w4, bias, y, N * H * W, Cin, Cout, ab, pre, post, dtype_code(y.dtype))
@@ -1001,9 +1024,10 @@ def conv_bn_act(x, w, bias=None, stride=1, pad=0, bn=None, pre_act=None, post_ac
     return y.squeeze(2) if tok else y
 
 
-def _eval_ab(bn, C, device):
+def _eval_ab(bn, C, device, sl=slice(None)):
+    """{a[C], b[C]} of an eval-mode BatchNorm bn = (gamma, beta, running_mean, running_var, eps); sl: the channels of one output slab"""
     ab = torch.empty(2 * C, device=device, dtype=torch.float32)
-    lib.bn_eval_ab(C, bn[0], bn[1], float(bn[4]), bn[2], bn[3], torch.empty(2 * C, device=device, dtype=torch.float32), ab)
+    lib.bn_eval_ab(C, bn[0][sl], bn[1][sl], float(bn[4]), bn[2][sl], bn[3][sl], torch.empty(2 * C, device=device, dtype=torch.float32), ab)
     return ab
 
 
@@ -1057,14 +1081,37 @@ def bn2_add_act_eval(xa, bnA, xb, bnB, pre_act='lrelu', act_kind='gelu'):
     _chk(xa, xb)
     C = xa.shape[-1]
     M = xa.numel() // C
-    abs_ = []
-    for bn in (bnA, bnB):
-        ab = torch.empty(2 * C, device=xa.device, dtype=torch.float32)
-        lib.bn_eval_ab(C, bn[0], bn[1], float(bn[4]), bn[2], bn[3], torch.empty(2 * C, device=xa.device, dtype=torch.float32), ab)
-        abs_.append(ab)
+    abA, abB = _eval_ab(bnA, C, xa.device), _eval_ab(bnB, C, xa.device)
     y = torch.empty_like(xa)
-    lib.bn2_add_act_fwd(xa, xb, y, M, C, abs_[0], abs_[1], ACT[pre_act], ACT[act_kind], dtype_code(xa.dtype))
+    lib.bn2_add_act_fwd(xa, xb, y, M, C, abA, abB, ACT[pre_act], ACT[act_kind], dtype_code(xa.dtype))
     return y
+
+
+def _scale_rows(dy, scale):
+    """scale[b] * dy[b] (the DropPath scale of a residual branch in its backward); dy itself without a scale"""
+    if scale is None:
+        return dy
+    B = dy.shape[0]
+    dz = torch.empty_like(dy)
+    lib.scale_rows(dy, scale, dz, B, dy.numel() // B, dtype_code(dy.dtype))
+    return dz
+
+
+def _pw_backward(x, dz, w, wsrc, bsrc):
+    """-> (dx, dw, db) of a bf16 pointwise convolution / Linear z = x W^T + bias with a bias: ONE pass over dz (tcct_pw_bwd) where the shape allows, else the
+    transposed GEMM plus the weight gradient on the side stream"""
+    K, Cout = x.shape[-1], w.shape[0]
+    M = x.numel() // K
+    dx = torch.empty_like(x)
+    if _pw_bwd_ok(x, dz, K, K, Cout, 1, 1, 1, 0, 0):
+        dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
+        lib.pw_bwd(x, dz, w, None, dx, dw, db, M, K, Cout)
+        return dx, dw, db
+    lib.pw_fwd(dz, w, None, dx, M, Cout, K, 1, dtype_code(x.dtype))
+    with _wgrad_stream(_slot_written(wsrc, bsrc), x, dz):
+        dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
+        lib.pw_wgrad(x, dz, dw, db, M, K, Cout)
+    return dx, dw, db
 
 
 class _LinearResidual(_FastFunction):
@@ -1086,23 +1133,7 @@ class _LinearResidual(_FastFunction):
         x, w = ctx.saved_tensors
         wsrc, bsrc = ctx.params
         dy = _c(dy)
-        B, Nt, K = x.shape
-        Cout, M = w.shape[0], B * Nt
-        dz = dy
-        if ctx.scale is not None:
-            dz = torch.empty_like(dy)
-            lib.scale_rows(dy, ctx.scale, dz, B, dy.numel() // B, dtype_code(dy.dtype))
-        dx = torch.empty_like(x)
-        if FUSED_PW_BWD and _pw_bwd_ok(x, dz, K, K, Cout, 1, 1, 1, 0, 0):
-            dw = _grad_out(wsrc, tuple(w.shape))
-            db = _grad_out(bsrc)
-            lib.pw_bwd(x, dz, w, None, dx, dw, db, M, K, Cout)
-            return dx, _ret(dw, wsrc), _ret(db, bsrc), dy, None
-        lib.pw_fwd(dz, w, None, dx, M, Cout, K, 1, dtype_code(x.dtype))
-        with _wgrad_stream(_slot_written(wsrc, bsrc), x, dz):
-            dw = _grad_out(wsrc, tuple(w.shape))
-            db = _grad_out(bsrc)
-            lib.pw_wgrad(x, dz, dw, db, M, K, Cout)
+        dx, dw, db = _pw_backward(x, _scale_rows(dy, ctx.scale), w, wsrc, bsrc)
         return dx, _ret(dw, wsrc), _ret(db, bsrc), dy, None
 
 
@@ -1132,10 +1163,7 @@ class _GeluLinearResidual(_FastFunction):
         dy = _c(dy)
         B, Nt, K = x1.shape
         Cout, M = w.shape[0], B * Nt
-        dz = dy
-        if ctx.scale is not None:
-            dz = torch.empty_like(dy)
-            lib.scale_rows(dy, ctx.scale, dz, B, dy.numel() // B, dtype_code(dy.dtype))
+        dz = _scale_rows(dy, ctx.scale)
         dx1 = torch.empty_like(x1)
         dw = _grad_out(wsrc, tuple(w.shape))
         db = _grad_out(bsrc)
@@ -1170,12 +1198,9 @@ class _MlpTail(_FastFunction):
         dt2 = _as(dt2, t1.dtype)
         B, Nt, K = t1.shape
         M = B * Nt
-        dz = dt2
-        if ctx.scale is not None:
-            dz = torch.empty_like(dt2)
-            lib.scale_rows(dt2, ctx.scale, dz, B, dt2.numel() // B, dtype_code(dt2.dtype))
-        w1s = w1p if hasattr(w1p, '_grad_slot') or w1p._base is None else w1p._base
-        w2s = w2p if hasattr(w2p, '_grad_slot') or w2p._base is None else w2p._base
+        dz = _scale_rows(dt2, ctx.scale)
+        w1s = _param_of(w1p)
+        w2s = _param_of(w2p)
         dy1 = torch.empty_like(y1)
         dw2, db2 = _grad_out(w2s, tuple(w2.shape)), _grad_out(bias2p)
         lib.pw_bwd_gelu(y1, dz, w2, dy1, dw2, db2, M, K, K)
@@ -1190,7 +1215,7 @@ MLP_TAIL_FUSE = True      # False: LayerNorm2 keeps its own backward pass (A/B t
 
 
 def mlp_tail_ok(t1, cur2, w1, bias1, w2, bias2):
-    return (MLP_TAIL_FUSE and MLP_GELU_FUSE and FUSED_PW_BWD and torch.is_grad_enabled() and t1.dtype == torch.bfloat16 and t1.dim() == 3 and t1.shape[-1] == 64
+    return (MLP_TAIL_FUSE and MLP_GELU_FUSE and torch.is_grad_enabled() and t1.dtype == torch.bfloat16 and t1.dim() == 3 and t1.shape[-1] == 64
             and cur2.shape == t1.shape and tuple(w1.shape) == (64, 64) and tuple(w2.shape) == (64, 64) and bias1 is not None and bias2 is not None
             and t1.is_contiguous() and cur2.is_contiguous() and t1.numel() * 2 < 2 ** 31)
 
@@ -1201,7 +1226,7 @@ def mlp_tail(t1, cur2, mr2, g2, b2, w1, bias1, w2, bias2, scale=None):
 
 
 def gelu_linear_residual_ok(x1, w, bias, res):
-    return (MLP_GELU_FUSE and FUSED_PW_BWD and torch.is_grad_enabled() and x1.dtype == torch.bfloat16 and x1.dim() == 3 and w.dim() == 2
+    return (MLP_GELU_FUSE and torch.is_grad_enabled() and x1.dtype == torch.bfloat16 and x1.dim() == 3 and w.dim() == 2
             and x1.shape[-1] in (64, 96) and w.shape[0] == x1.shape[-1] and w.shape[1] == x1.shape[-1] and bias is not None
             and res.shape == x1.shape and x1.numel() * 2 < 2 ** 31)
 
@@ -1238,19 +1263,7 @@ class _Conv1x1AndSum(_FastFunction):
         else:
             dz = torch.empty_like(gs)
             lib.add(_c(gd), _c(gs), dz, dz.numel(), dtype_code(dz.dtype))
-        N_, H, W_, K = x.shape
-        Cout, M = w.shape[0], N_ * H * W_
-        dx = torch.empty_like(x)
-        if FUSED_PW_BWD and _pw_bwd_ok(x, dz, K, K, Cout, 1, 1, 1, 0, 0):
-            dw = _grad_out(wsrc, tuple(w.shape))
-            db = _grad_out(bsrc)
-            lib.pw_bwd(x, dz, w, None, dx, dw, db, M, K, Cout)
-            return dx, _ret(dw, wsrc), _ret(db, bsrc), (None if gs is None else _c(gs))
-        lib.pw_fwd(dz, w, None, dx, M, Cout, K, 1, dtype_code(x.dtype))
-        with _wgrad_stream(_slot_written(wsrc, bsrc), x, dz):
-            dw = _grad_out(wsrc, tuple(w.shape))
-            db = _grad_out(bsrc)
-            lib.pw_wgrad(x, dz, dw, db, M, K, Cout)
+        dx, dw, db = _pw_backward(x, dz, w, wsrc, bsrc)
         return dx, _ret(dw, wsrc), _ret(db, bsrc), (None if gs is None else _c(gs))
 
 
@@ -1289,49 +1302,34 @@ class _UpSkipConv(_FastFunction):
         if gd is None and gs is None:
             return None, None, None, None, None, None
         Cout, M = w.shape[0], N_ * Ho * Wo
-        if (gd is not None and gs is not None and DY2_FUSE and FUSED_PW_BWD and C == 32 and Cout == 32 and u.dtype == torch.bfloat16
-                and _pw_bwd_ok(u, _c(gs), C, C, Cout, 1, 1, 1, 0, 0)):
-            # the two output gradients are summed while the backward kernel stages its tiles: no add pass
-            gd, gs = _c(gd), _c(gs)
-            du, dskip = torch.empty_like(u), torch.empty_like(u)
-            dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
-            lib.pw_bwd_residual2_sum(u, gd, gs, w, gs, dskip, du, dw, db, M, C, Cout)
-            dy = torch.empty((N_, H, W_, C), device=u.device, dtype=u.dtype)
-            lib.bilinear_bwd(du, dy, N_, H, W_, C, Ho, Wo, align, dtype_code(u.dtype))
-            return dy, dskip, _ret(dw, wsrc), _ret(db, bsrc), None, None
-        if gd is None or gs is None:
-            dz = _c(gd if gs is None else gs)
-        else:
-            dz = torch.empty_like(gs)
-            lib.add(_c(gd), _c(gs), dz, dz.numel(), dtype_code(dz.dtype))
-        du = torch.empty_like(u)
-        fused = FUSED_PW_BWD and _pw_bwd_ok(u, dz, C, C, Cout, 1, 1, 1, 0, 0)
-        if fused:       # both input gradients and the weight / bias gradients from ONE pass over dz
-            dw = _grad_out(wsrc, tuple(w.shape))
-            db = _grad_out(bsrc)
-            if gs is not None:
-                dskip = torch.empty_like(u)
-                lib.pw_bwd_residual2(u, dz, w, _c(gs), dskip, du, dw, db, M, C, Cout)
-            else:
-                lib.pw_bwd(u, dz, w, None, du, dw, db, M, C, Cout)
-                dskip = du
-        elif gs is not None:
-            dskip = torch.empty_like(u)
-            lib.pw_dgrad_residual(dz, w, _c(gs), dskip, du, M, Cout, C)
-        else:
-            lib.pw_fwd(dz, w, None, du, M, Cout, C, 1, dtype_code(u.dtype))
+        gd, gs = (None if gd is None else _c(gd)), (None if gs is None else _c(gs))
+        dw = dz = None
+        if gs is None:          # only d was used: the skip tensor's gradient is the one through u
+            du, dw, db = _pw_backward(u, gd, w, wsrc, bsrc)
             dskip = du
+        else:
+            du, dskip = torch.empty_like(u), torch.empty_like(u)
+            if gd is not None and C == 32 and Cout == 32 and u.dtype == torch.bfloat16 and _pw_bwd_ok(u, gs, C, C, Cout, 1, 1, 1, 0, 0):
+                # the two output gradients are summed while the backward kernel stages its tiles: no add pass
+                dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
+                lib.pw_bwd_residual2_sum(u, gd, gs, w, gs, dskip, du, dw, db, M, C, Cout)
+            else:
+                dz = gs
+                if gd is not None:
+                    dz = torch.empty_like(gs)
+                    lib.add(gd, gs, dz, dz.numel(), dtype_code(dz.dtype))
+                if _pw_bwd_ok(u, dz, C, C, Cout, 1, 1, 1, 0, 0):       # both input gradients and the weight / bias gradients from ONE pass over dz
+                    dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
+                    lib.pw_bwd_residual2(u, dz, w, gs, dskip, du, dw, db, M, C, Cout)
+                else:
+                    lib.pw_dgrad_residual(dz, w, gs, dskip, du, M, Cout, C)
         dy = torch.empty((N_, H, W_, C), device=u.device, dtype=u.dtype)
         lib.bilinear_bwd(du, dy, N_, H, W_, C, Ho, Wo, align, dtype_code(u.dtype))
-        if not fused:
+        if dw is None:
             with _wgrad_stream(_slot_written(wsrc, bsrc), u, dz):
-                dw = _grad_out(wsrc, tuple(w.shape))
-                db = _grad_out(bsrc)
+                dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
                 lib.pw_wgrad(u, dz, dw, db, M, C, Cout)
         return dy, dskip, _ret(dw, wsrc), _ret(db, bsrc), None, None
-
-
-DY2_FUSE = True      # False: the decoder blocks add their two output gradients in a separate pass (A/B timing)
 
 
 def up_skip_conv(y, skip, w, bias, align_corners=True, want_plain=True):
@@ -1392,7 +1390,7 @@ class _UpSkipConvT32(_FastFunction):
 
 
 def up_skip_conv_t32_ok(y, skip, w1, b1, w2, b2):
-    return (TAIL_COMPOSE and FUSED_PW_BWD and y.dtype == torch.bfloat16 and skip.dtype == y.dtype and y.dim() == 4       # (the caller requires a train-mode block)
+    return (TAIL_COMPOSE and y.dtype == torch.bfloat16 and skip.dtype == y.dtype and y.dim() == 4       # (the caller requires a train-mode block)
             and y.shape[-1] == 32 and skip.shape[-1] == 32 and tuple(skip.shape[1:3]) == (2 * y.shape[1], 2 * y.shape[2])
             and tuple(w1.shape) == (32, 32, 1, 1) and tuple(w2.shape) == (32, 32, 1, 1) and b1 is not None and b2 is not None
             and w1.is_contiguous() and w2.is_contiguous() and skip.numel() * 2 < 2 ** 31)
@@ -1638,11 +1636,11 @@ class _PwCat2(_FastFunction):
         y = torch.empty((N_, H, W_, Cout), device=a.device, dtype=a.dtype)
         sums = None
         if stats_box is not None and Cout % 32 == 0 and Cout <= 128:
-            sums = ZERO.get((2 * Cout,), torch.float64, a.device) if ZERO.active else torch.zeros(2 * Cout, device=a.device, dtype=torch.float64)
+            sums = _zeros((2 * Cout,), torch.float64, a.device)
             stats_box[1] = sums
         lib.pw_fwd_cat2(a, b, Ca, w, None, y, M, Ca + Cb, Cout, sums, stats_box[0] if sums is not None else 0)
         ctx.save_for_backward(a, b, w)
-        wsrc = w if hasattr(w, '_grad_slot') or w._base is None else w._base
+        wsrc = _param_of(w)
         ctx.wsrc = wsrc
         return y
 
@@ -1653,7 +1651,7 @@ class _PwCat2(_FastFunction):
         N_, H, W_, Ca = a.shape
         Cb, Cout, M = b.shape[-1], w.shape[0], N_ * H * W_
         da, db_ = torch.empty_like(a), torch.empty_like(b)
-        if (FUSED_PW_BWD and Ca == 64 and Cb == 64 and Cout % 32 == 0 and Cout <= 128 and dy.dtype == torch.bfloat16
+        if (Ca == 64 and Cb == 64 and Cout % 32 == 0 and Cout <= 128 and dy.dtype == torch.bfloat16
                 and a.numel() * 2 < 2 ** 31 and dy.numel() * 2 < 2 ** 31):
             dw = _grad_out(ctx.wsrc, tuple(w.shape))
             lib.pw_bwd_cat2(a, b, dy, w, da, db_, dw, M, Ca + Cb, Cout)
@@ -1709,7 +1707,7 @@ class _ConvC3(_FastFunction):
         y = torch.empty((B, Ho, Wo, 32), device=x4.device, dtype=torch.bfloat16)
         sums = None
         if stats_box is not None:
-            sums = ZERO.get((64,), torch.float64, x4.device) if ZERO.active else torch.zeros(64, device=x4.device, dtype=torch.float64)
+            sums = _zeros((64,), torch.float64, x4.device)
             stats_box[1] = sums
         lib.c3_fwd(x4, w, bias, y, B, H, W, stride, sums, stats_box[0] if stats_box is not None else 0, None, 0, 0)
         ctx.save_for_backward(x4)
@@ -1746,8 +1744,7 @@ def conv3x3_c3(x4, w, bias, stride=1, stats_pre=None, infer_bn=None, post_act=No
             if torch.is_grad_enabled() and w.requires_grad:
                 raise TcctError('conv3x3_c3(infer_bn=...) is inference-only (call it under torch.no_grad())')
             B, H, W, _ = x4.shape
-            ab = torch.empty(64, device=x4.device, dtype=torch.float32)
-            lib.bn_eval_ab(32, infer_bn[0], infer_bn[1], float(infer_bn[4]), infer_bn[2], infer_bn[3], torch.empty(64, device=x4.device, dtype=torch.float32), ab)
+            ab = _eval_ab(infer_bn, 32, x4.device)
             y = torch.empty((B, (H - 1) // stride + 1, (W - 1) // stride + 1, 32), device=x4.device, dtype=torch.bfloat16)
             if C3_BN_FUSE and ACT[post_act] in (0, ACT['hswish']):      # round 6: the recompute kernel's normalising pass with the eval coefficients (0.10 vs 0.28 ms at level 0)
                 lib.c3_bn_fwd_eval(x4, w, bias, y, B, H, W, stride, ab, ACT[post_act])
@@ -1780,7 +1777,7 @@ class _ConvC3BN(_FastFunction):
         B, H, W, _ = x4.shape
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         z = torch.empty((B, Ho, Wo, 32), device=x4.device, dtype=torch.bfloat16)
-        sums = ZERO.get((64,), torch.float64, x4.device) if ZERO.active else torch.zeros(64, device=x4.device, dtype=torch.float64)
+        sums = _zeros((64,), torch.float64, x4.device)
         mean_rstd = torch.empty(64, device=x4.device, dtype=torch.float32)
         ab = torch.empty(64, device=x4.device, dtype=torch.float32)
         lib.c3_bn_fwd_train(x4, w, bias, z, B, H, W, stride, sums, gamma, beta, eps, momentum, rm, rv, nbt, mean_rstd, ab, post)
@@ -1796,7 +1793,7 @@ class _ConvC3BN(_FastFunction):
         B, H, W, _ = x4.shape
         M = dz.numel() // 32
         dev = x4.device
-        raw = ZERO.get((64,), torch.float64, dev) if ZERO.active else torch.zeros(64, device=dev, dtype=torch.float64)
+        raw = _zeros((64,), torch.float64, dev)
         coef = torch.empty(160, device=dev, dtype=torch.float32)
         # nothing downstream waits for this node (the image has no gradient): all of it runs beside the other encoder's tail on the weight-gradient stream
         with _wgrad_stream(_slot_written(w, bias, gamma, beta), x4, dz, coef, mean_rstd, ab):
@@ -1808,8 +1805,8 @@ class _ConvC3BN(_FastFunction):
                 if C3_BWD_FORM != _C3_FORM_SET[0]:
                     lib.c3_bn_bwd_prefetch(C3_BWD_FORM)
                     _C3_FORM_SET[0] = C3_BWD_FORM
-                work = ZERO.get((4160,), torch.float32, dev) if ZERO.active else torch.zeros(4160, device=dev, dtype=torch.float32)
-                s96 = ZERO.get((96,), torch.float64, dev) if ZERO.active else torch.zeros(96, device=dev, dtype=torch.float64)
+                work = _zeros((4160,), torch.float32, dev)
+                s96 = _zeros((96,), torch.float64, dev)
                 lib.c3_bn_bwd_onepass(x4, w, bias, dz, B, H, W, stride, mean_rstd, ab, work, s96, dw, dbias, dg, db_, post)
             else:
                 lib.c3_bn_bwd_reduce(x4, w, bias, dz, B, H, W, stride, ab, raw, post)
@@ -1854,11 +1851,11 @@ class _DwConv(_FastFunction):
                 raise TcctError('dwconv3x3(deferred=...): plain convolution with C % 4 == 0, C <= 256 only')
             sums = None
             if stats_box is not None:
-                sums = ZERO.get((2 * C,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * C, device=x.device, dtype=torch.float64)
+                sums = _zeros((2 * C,), torch.float64, x.device)
                 stats_box[0] = sums
             lib.dwconv3x3_fwd_xaff(x, xab, w, bias, y, N, H, W, C, stride, sums, dtype_code(x.dtype))
         elif stats_box is not None and C % 4 == 0 and C <= 256:
-            sums = ZERO.get((2 * C,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * C, device=x.device, dtype=torch.float64)
+            sums = _zeros((2 * C,), torch.float64, x.device)
             lib.dwconv3x3_fwd_bnstats(x, w, bias, y, N, H, W, C, stride, int(add_input), sums, dtype_code(x.dtype))
             stats_box[0] = sums
         else:
@@ -1883,7 +1880,7 @@ class _DwConv(_FastFunction):
                 lib.dwconv3x3_dgrad_add(dy, w, _as(dskip, x.dtype), dx, N, H, W, C, stride, int(add_input), dtype_code(x.dtype))
             elif ctx.xab is not None and ctx.xlink is not None and stride == 1 and BN_FUSE_RED and BN_RED_DW:
                 # x is y_prev of the pending BatchNorm: its two backward sums come out of this launch (raw form), its own reduction pass is skipped
-                raw = ZERO.get((2 * C,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * C, device=x.device, dtype=torch.float64)
+                raw = _zeros((2 * C,), torch.float64, x.device)
                 lib.dwconv3x3_dgrad_bnred(dy, w, x, ctx.xab, dx, raw, N, H, W, C, dtype_code(x.dtype))
                 ctx.xlink.sums = raw
             else:
@@ -2031,7 +2028,7 @@ class _PwConvBN(_FastFunction):
         N = w.shape[0]
         M = x.numel() // K1
         y = torch.empty(x.shape[:-1] + (N,), device=x.device, dtype=x.dtype)
-        sums = ZERO.get((2 * N,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * N, device=x.device, dtype=torch.float64)
+        sums = _zeros((2 * N,), torch.float64, x.device)
         if xdef is not None:
             lib.pw_fwd_bnstats_xaff(x, xdef, w, bias, y, M, K, N, sums)
         elif x2 is not None:
@@ -2047,7 +2044,7 @@ class _PwConvBN(_FastFunction):
             z = torch.empty_like(y)
             lib.bn_apply_train(y, res, z, M, N, sums, gamma, beta, eps, momentum, rm, rv, nbt, mean_rstd, ab, 0, post, dtype_code(y.dtype))
         ctx.save_for_backward(x, x2, w, y, mean_rstd, ab)
-        wsrc = w if hasattr(w, '_grad_slot') or w._base is None else w._base
+        wsrc = _param_of(w)
         ctx.cfg = (post, res is not None, wsrc, bias, gamma, beta, link, prev, M, K, N)
         ctx.xdef = xdef
         link.y, link.ab = y, ab
@@ -2111,8 +2108,8 @@ class _Affine2Add(_FastFunction):
             dz = _as(dz, y1.dtype)
             C = y1.shape[-1]
             dev = y1.device
-            r1 = ZERO.get((2 * C,), torch.float64, dev) if ZERO.active else torch.zeros(2 * C, device=dev, dtype=torch.float64)
-            r2 = ZERO.get((2 * C,), torch.float64, dev) if ZERO.active else torch.zeros(2 * C, device=dev, dtype=torch.float64)
+            r1 = _zeros((2 * C,), torch.float64, dev)
+            r2 = _zeros((2 * C,), torch.float64, dev)
             lib.bn_bwd_reduce2_raw(y1, y2, dz, y1.numel() // C, C, r1, r2, dtype_code(y1.dtype))
             l1.sums, l2.sums = r1, r2
         return dz, None, dz, None, None, None
@@ -2150,7 +2147,7 @@ class _BatchNormDeferred(_FastFunction):
         if fused is not None and fused[1] == 0 and fused[0].numel() == 2 * C:
             sums = fused[0]
         else:
-            sums = ZERO.get((2 * C,), torch.float64, x.device) if ZERO.active else torch.zeros(2 * C, device=x.device, dtype=torch.float64)
+            sums = _zeros((2 * C,), torch.float64, x.device)
             lib.bn_stats(x, M, C, 0, sums, dtype_code(x.dtype))
         mean_rstd = torch.empty(2 * C, device=x.device, dtype=torch.float32)
         ab = torch.empty(2 * C, device=x.device, dtype=torch.float32)
@@ -2188,7 +2185,7 @@ def batchnorm_deferred(x, gamma, beta, running_mean, running_var, num_batches_tr
 
 def pw_conv_bn_ok(x, w, bias, bn_training, pre_act, post_act, x2=None, prev=None):
     """shapes / modes the fused node takes: train mode with gradients, bf16 rows, 1x1 weights, K and N in the kernel's table"""
-    if not (BN_FUSE and FUSED_PW_BWD and bn_training and torch.is_grad_enabled() and ACT[pre_act] == 0):
+    if not (BN_FUSE and bn_training and torch.is_grad_enabled() and ACT[pre_act] == 0):
         return False
     if x.dtype != torch.bfloat16 or x.dim() != 4 or not x.is_cuda or (w.dim() == 4 and tuple(w.shape[2:]) != (1, 1)):
         return False
@@ -2489,10 +2486,7 @@ class _Residual(_FastFunction):
     def backward(ctx, dy):
         (scale,) = ctx.saved_tensors
         dy = _c(dy)
-        B = dy.shape[0]
-        dz = torch.empty_like(dy)
-        lib.scale_rows(dy, scale, dz, B, dy.numel() // B, dtype_code(dy.dtype))
-        return dy, dz, None
+        return dy, _scale_rows(dy, scale), None
 
 
 def residual(x, z, scale=None):
