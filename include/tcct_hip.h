@@ -110,6 +110,13 @@ int tcct_bn_pool_fwd_train(const void* x, void* z, void* pooled, void* amax, int
  * writing that sum (dskip nullable); sums fp64 [2C] scratch, dgamma / dbeta fp32 [C] overwritten */
 int tcct_bn_pool_bwd(const void* x, const void* dpool, const void* dskip, const void* amax, void* dx, int N, int H, int W, int C, const float* mean_rstd,
                      const float* ab, int pre_act, int post_act, double* sums, float* dgamma, float* dbeta, int dtype, tcct_stream_t stream);
+/* the same with dskip given by its factors, for the level whose only other consumer is the composed level-0 head logits0 = up(Wa y) + Wb z + c
+ * (ops._UpSkipConvT32AuxLow): dskip = round_bf16(dl wb) with dl fp32 [N,H,W,nc] the logit gradient and wb fp32 [nc,32], 2 <= nc <= 8 -- element for
+ * element what tcct_conv2d_dgrad(dl, wb, dskip) would store, formed on load by both kernels, so neither that launch nor the 32-channel tensor
+ * exists.  bf16, C = 32, pre_act LeakyReLU, post_act none only; dl 8-byte aligned. */
+int tcct_bn_pool_bwd_lowrank(const void* x, const void* dpool, const float* dl, const float* wb, int nc, const void* amax, void* dx, int N, int H, int W,
+                             int C, const float* mean_rstd, const float* ab, int pre_act, int post_act, double* sums, float* dgamma, float* dbeta,
+                             int dtype, tcct_stream_t stream);
 /* y = post(a*pre(x)+b) + res (res, y like x): the normalisation pass with the residual / branch sum that follows it folded in
  * (InvRes `x + conv2(f)`, nets/tcct.py:563-572; `tran_vit(x) + tran_cnn(c)`, :1012-1015) */
 int tcct_bn_apply_add(const void* x, const void* res, void* y, int64_t M, int C, const float* ab, int pre_act, int post_act, int dtype,

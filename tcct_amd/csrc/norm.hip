@@ -574,6 +574,154 @@ __global__ void k_bn_pool_bwd_apply(const T* __restrict__ x, const T* __restrict
         }
     }
 }
+// ---- the same two kernels with the skip gradient in LOW-RANK form (level 0 under the composed head, ops._UpSkipConvT32AuxLow) ----------------
+// The only other consumer of z is the head logits0 = up(Wa y) + Wb z + c, so dskip = Wb^T dl: n_class <= 8 fp32 numbers per pixel expanded to 32
+// bf16 channels by tcct_conv2d_dgrad(dl, wb, dskip) (k_conv1x1_smallcin<float, bf16>), written once and read by both kernels above.  Here both read
+// dl (20 B per pixel at n_class = 5 instead of 64) and form their four channels of dskip on load; that launch and the tensor disappear.
+// C = 32: the 8 lanes of a window need the same 4 NC floats, a wave (8 consecutive windows of one window row) needs 2 x 16 NC CONTIGUOUS floats.
+// The wave fetches them with one 8-byte load per lane and image row into its own LDS slot and every lane reads its window's floats back as NC
+// 8-byte broadcast reads per image row (4 NC scalar global loads per lane would make the kernels load-issue bound).
+#define LR_SLOT 256     // floats per wave: 2 image rows x 128 (16 NC <= 128)
+template <int NC>
+__device__ __forceinline__ void lowrank_stage(float* __restrict__ slot, const float* __restrict__ dl0 /* pixel (2 ho, 2 wo0) */, int64_t row_stride /* W NC */,
+                                              int nwin /* valid windows of the wave, 1..8 */, int lane) {
+    wave_lds_fence();           // the previous round's reads of the slot come first
+    if (lane < nwin * NC) {
+        const float2 r0 = reinterpret_cast<const float2*>(dl0)[lane], r1 = reinterpret_cast<const float2*>(dl0 + row_stride)[lane];
+        reinterpret_cast<float2*>(slot)[lane] = r0;
+        reinterpret_cast<float2*>(slot + LR_SLOT / 2)[lane] = r1;
+    }
+    wave_lds_fence();
+}
+// e[q].v[k] = dskip[pixel q of window wl][c0 + k] as the removed launch would have stored it and ld4 read it back: the sum over j ascending from a
+// zero accumulator (`a += dl[j] * wb[j][c]`, the statement and contraction of k_conv1x1_smallcin with no bias), rounded by the same packed convert
+template <int NC>
+__device__ __forceinline__ void lowrank_dskip(const float* __restrict__ slot, int wl, const float (&w)[NC][4], f4 (&e)[4]) {
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        float f[2 * NC];
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            const float2 t = reinterpret_cast<const float2*>(slot + rr * (LR_SLOT / 2) + wl * 2 * NC)[i];
+            f[2 * i] = t.x; f[2 * i + 1] = t.y;
+        }
+#pragma unroll
+        for (int col = 0; col < 2; ++col) {
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) a[k] += f[col * NC + j] * w[j][k];
+            const uint32_t lo = pack_bf16x2(a[0], a[1]), hi = pack_bf16x2(a[2], a[3]);
+            f4& o = e[rr * 2 + col];
+            o.v[0] = __uint_as_float(lo << 16); o.v[1] = __uint_as_float(lo & 0xffff0000u);
+            o.v[2] = __uint_as_float(hi << 16); o.v[3] = __uint_as_float(hi & 0xffff0000u);
+        }
+    }
+}
+// Register budget: a 1024-thread block is 4 waves per SIMD, i.e. 128 VGPRs per lane, and __launch_bounds__(NBR) makes the compiler SPILL beyond that instead of
+// failing.  The resource report gives 111 / 112 / 118 / 124 / 122 / 119 / 128 VGPRs for NC = 2..8, no scratch: NC = 8 sits exactly on the ceiling.  Re-read the
+// report (-Rpass-analysis=kernel-resource-usage, ScratchSize 0) after any change that adds a live value to the loop or after a compiler update; the way out is Wb
+// in LDS (4 NC registers fewer, NC broadcast ds_read_b128 more per window).
+template <int NC>
+__global__ void __launch_bounds__(NBR) k_bn_pool_bwd_reduce_lr(const bf16* __restrict__ x, const bf16* __restrict__ dpool, const float* __restrict__ dl,
+                                                               const float* __restrict__ wb, const unsigned char* __restrict__ amax, int N, int H, int W,
+                                                               const float* __restrict__ mean_rstd, double* __restrict__ sums) {
+    constexpr int C = 32, C4 = 8, R = NBR / C4;
+    __shared__ __attribute__((aligned(16))) float sm[NBR * 4];      // first the waves' dl slots (16 x LR_SLOT floats), then the block combine
+    const int Ho = H >> 1, Wo = W >> 1;
+    const int t = threadIdx.x, lane = t & 63, wl = lane >> 3, cv = t & 7, c0 = cv * 4;
+    float* slot = sm + (t >> 6) * LR_SLOT;
+    float s[4], q2[4], mu[4], rs[4], w[NC][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { s[k] = q2[k] = 0.f; mu[k] = mean_rstd[c0 + k]; rs[k] = mean_rstd[C + c0 + k]; }
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[j][k] = wb[j * C + c0 + k];
+    for (int row = blockIdx.x; row < N * Ho; row += gridDim.x) {
+        const int n = row / Ho, ho = row - n * Ho;
+        for (int wo0 = (t >> 6) * 8; wo0 < Wo; wo0 += R) {          // wave-uniform: the wave stages dl for its 8 windows together
+            const int wo = wo0 + wl;
+            const int64_t pix0 = ((int64_t)n * H + 2 * ho) * W + 2 * wo0;
+            lowrank_stage<NC>(slot, dl + pix0 * NC, (int64_t)W * NC, min(8, Wo - wo0), lane);
+            if (wo >= Wo) continue;
+            const int64_t b00 = (pix0 + 2 * wl) * C + c0;
+            const int64_t offs[4] = {b00, b00 + C, b00 + (int64_t)W * C, b00 + (int64_t)W * C + C};
+            f4 v[4], e[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = ld4(x + offs[q]);
+            const int64_t p = (int64_t)row * Wo + wo;
+            const f4 g = ld4(dpool + p * C + c0);
+            const unsigned am = amax[p * C4 + cv];
+            lowrank_dskip<NC>(slot, wl, w, e);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float u = actf<TCCT_ACT_LRELU>(TCCT_ACT_LRELU, v[q].v[k]);
+                    const float dz = e[q].v[k] + (((am >> (2 * k)) & 3u) == (unsigned)q ? g.v[k] : 0.f);
+                    s[k] += dz; q2[k] += dz * (u - mu[k]) * rs[k];
+                }
+        }
+    }
+    __syncthreads();            // every wave is done with its slot before the combine reuses the array
+    bn_block_reduce2<4>(sm, s, q2, t, C, C4, R, sums);
+}
+template <int NC>
+__global__ void __launch_bounds__(NB) k_bn_pool_bwd_apply_lr(const bf16* __restrict__ x, const bf16* __restrict__ dpool, const float* __restrict__ dl,
+                                                             const float* __restrict__ wb, const unsigned char* __restrict__ amax, bf16* __restrict__ dx,
+                                                             int N, int H, int W, const float* __restrict__ mean_rstd, const float* __restrict__ ab,
+                                                             const double* __restrict__ sums, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    constexpr int C = 32, C4 = 8;
+    __shared__ __attribute__((aligned(16))) float sm[(NB / 64) * LR_SLOT];
+    const int Ho = H >> 1, Wo = W >> 1;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63, wl = lane >> 3;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < C) { dbeta[threadIdx.x] = (float)sums[threadIdx.x]; dgamma[threadIdx.x] = (float)sums[C + threadIdx.x]; }
+    const int wo0 = (i - lane) >> 3, wo = wo0 + wl, c0 = (i & 7) * 4;
+    if (wo0 >= Wo) return;                                          // the whole wave: lanes of a partly valid wave stay for the staging
+    float* slot = sm + (threadIdx.x >> 6) * LR_SLOT;
+    const float invM = 1.f / (float)((int64_t)N * H * W);
+    float a_[4], mu[4], rs[4], s1[4], s2[4], w[NC][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = c0 + k;
+        a_[k] = ab[c]; mu[k] = mean_rstd[c]; rs[k] = mean_rstd[C + c];
+        s1[k] = (float)sums[c] * invM; s2[k] = (float)sums[C + c] * invM;
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[j][k] = wb[j * C + c0 + k];
+    for (int row = blockIdx.y; row < N * Ho; row += gridDim.y) {
+        const int n = row / Ho, ho = row - n * Ho;
+        const int64_t pix0 = ((int64_t)n * H + 2 * ho) * W + 2 * wo0;
+        lowrank_stage<NC>(slot, dl + pix0 * NC, (int64_t)W * NC, min(8, Wo - wo0), lane);
+        if (wo >= Wo) continue;
+        const int64_t b00 = (pix0 + 2 * wl) * C + c0;
+        const int64_t offs[4] = {b00, b00 + C, b00 + (int64_t)W * C, b00 + (int64_t)W * C + C};
+        f4 v[4], e[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = ld4(x + offs[q]);
+        const int64_t p = (int64_t)row * Wo + wo;
+        const f4 g = ld4(dpool + p * C + c0);
+        const unsigned am = amax[p * C4 + (c0 >> 2)];
+        lowrank_dskip<NC>(slot, wl, w, e);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            f4 o;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float u = actf<TCCT_ACT_LRELU>(TCCT_ACT_LRELU, v[q].v[k]);
+                const float dz = e[q].v[k] + (((am >> (2 * k)) & 3u) == (unsigned)q ? g.v[k] : 0.f);
+                const float xh = (u - mu[k]) * rs[k];
+                o.v[k] = a_[k] * (dz - s1[k] - xh * s2[k]);
+                o.v[k] *= actg<TCCT_ACT_LRELU>(TCCT_ACT_LRELU, v[q].v[k]);
+            }
+            st4(dx + offs[q], o);
+        }
+    }
+}
 static bool bn_pool_ok(int N, int H, int W, int C) { return C % 4 == 0 && C >= 4 && C <= NB && NB % (C / 4) == 0 && H % 2 == 0 && W % 2 == 0 && H >= 2 && W >= 2 && N >= 1; }
 static inline dim3 bn_pool_grid(int per_row, int64_t rows) {
     const int gx = (per_row + NB - 1) / NB;
@@ -617,6 +765,34 @@ extern "C" int tcct_bn_pool_bwd(const void* x, const void* dpool, const void* ds
     BN_POOL_KINDS(TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_bn_pool_bwd_apply<T, PRE, POST>), bn_pool_grid((W / 2) * (C / 4), rows), dim3(NB), 0, st, (const T*)x,
                                                           (const T*)dpool, (const T*)dskip, (const unsigned char*)amax, (T*)dx, N, H, W, C, mean_rstd, ab, sums,
                                                           pre_act, post_act, dgamma, dbeta)));
+    TCCT_LAUNCH_OK();
+}
+/* tcct_bn_pool_bwd with dskip given as its factors: dskip = round_bf16(dl wb), dl fp32 [N,H,W,nc] (the head's logit gradient), wb fp32 [nc,32]
+ * (2 <= nc <= 8) -- element for element what tcct_conv2d_dgrad(dl, wb, dskip) stores, formed on load by both kernels.  bf16, C = 32, LeakyReLU in
+ * front and nothing behind only (the encoder's level-0 node; ops.bn_pool_lowrank_ok is the same test). */
+static bool bn_pool_bwd_lowrank_ok(int C, int nc, int pre_act, int post_act, int dtype) {
+    return C == 32 && nc >= 2 && nc <= 8 && pre_act == TCCT_ACT_LRELU && post_act == TCCT_ACT_NONE && dtype == TCCT_BF16;
+}
+extern "C" int tcct_bn_pool_bwd_lowrank(const void* x, const void* dpool, const float* dl, const float* wb, int nc, const void* amax, void* dx, int N,
+                                        int H, int W, int C, const float* mean_rstd, const float* ab, int pre_act, int post_act, double* sums,
+                                        float* dgamma, float* dbeta, int dtype, tcct_stream_t stream) {
+    TCCT_CHECK(bn_pool_ok(N, H, W, C), "bn_pool_bwd_lowrank: needs even H, W (got %d,%d,%d)", H, W, C);
+    TCCT_CHECK(bn_pool_bwd_lowrank_ok(C, nc, pre_act, post_act, dtype), "bn_pool_bwd_lowrank: bf16, C=32, nc 2..8, lrelu/none only (C=%d nc=%d)", C, nc);
+    TCCT_CHECK(dpool != nullptr && amax != nullptr && dl != nullptr && wb != nullptr, "bn_pool_bwd_lowrank: NULL argument");
+    TCCT_CHECK(((uintptr_t)dl & 7) == 0, "bn_pool_bwd_lowrank: dl must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (!tcct_skip_zero_fill() && hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, st) != hipSuccess) { tcct_set_error("bn_pool_bwd_lowrank: memset failed"); return -2; }
+    const int64_t rows = (int64_t)N * (H / 2);
+    const int gr = rows < 512 ? (int)rows : 512;
+    const dim3 ga = bn_pool_grid((W / 2) * (C / 4), rows);
+#define LR_LAUNCH(NC) case NC: \
+        hipLaunchKernelGGL((k_bn_pool_bwd_reduce_lr<NC>), dim3(gr), dim3(NBR), 0, st, (const bf16*)x, (const bf16*)dpool, dl, wb, (const unsigned char*)amax, N, H, W, \
+                           mean_rstd, sums); \
+        hipLaunchKernelGGL((k_bn_pool_bwd_apply_lr<NC>), ga, dim3(NB), 0, st, (const bf16*)x, (const bf16*)dpool, dl, wb, (const unsigned char*)amax, (bf16*)dx, N, H, W, \
+                           mean_rstd, ab, sums, dgamma, dbeta); \
+        break
+    switch (nc) { LR_LAUNCH(2); LR_LAUNCH(3); LR_LAUNCH(4); LR_LAUNCH(5); LR_LAUNCH(6); LR_LAUNCH(7); LR_LAUNCH(8); }
+#undef LR_LAUNCH
     TCCT_LAUNCH_OK();
 }
 

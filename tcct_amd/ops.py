@@ -222,7 +222,11 @@ def grad_mark(x, key):
     if _STEP['listener'] is None or not ZERO.active or not (torch.is_grad_enabled() and x.requires_grad):
         return x
     _STEP['marks'].setdefault(key, [0, 0])[0] += 1
-    return _GradMark.apply(x, key)
+    y = _GradMark.apply(x, key)
+    link = getattr(x, '_skip0', None)
+    if link is not None:        # the alias is the same edge: a low-rank gradient recipe (SKIP0_LOWRANK) passes this node's backward untouched
+        y._skip0 = link
+    return y
 
 
 def end_step():
@@ -1485,6 +1489,11 @@ class _UpSkipConvT32AuxLow(_FastFunction):
         ctx.save_for_backward(y, skip, wa, wb)
         ctx.params = (w1, b1, w2, b2, w3, b3)
         ctx.cfg = (N_, H, W_, C, Ho, Wo, int(align), nc)
+        # skip is the full-size output of a BatchNorm + pool node whose backward kernels can form Wb^T dl themselves (SKIP0_LOWRANK below)
+        link = getattr(skip, '_skip0', None) if SKIP0_LOWRANK else None
+        ctx.skip0 = link if (link is not None and link.ok and 2 <= nc <= 8 and ctx.needs_input_grad[1] and not grad_is_watched(skip)) else None
+        if ctx.skip0 is not None:
+            del link.recipes[:]         # a recipe an earlier backward pass filed and never delivered (it raised before the producer's node ran) must not be added to this one's
         return lg
 
     @staticmethod
@@ -1496,9 +1505,17 @@ class _UpSkipConvT32AuxLow(_FastFunction):
         F32_, BF_ = dtype_code(torch.float32), dtype_code(y.dtype)
         dz = torch.empty((N_, H, W_, nc), device=dev, dtype=torch.float32)
         lib.bilinear_bwd(dl, dz, N_, H, W_, nc, Ho, Wo, align, F32_)
-        dy, dskip = torch.empty_like(y), torch.empty_like(skip)
+        dy = torch.empty_like(y)
         lib.conv2d_dgrad(dz, wa, dy, N_, H, W_, 32, nc, 1, 1, 0, 0, F32_, BF_)
-        lib.conv2d_dgrad(dl, wb, dskip, N_, Ho, Wo, 32, nc, 1, 1, 0, 0, F32_, BF_)
+        if ctx.skip0 is not None:
+            # d loss / d skip = Wb^T dl has rank n_class: the producer's backward kernels form it on load from (dl, wb).  What autograd carries is a
+            # zero-stride expansion of one zero element (right shape and dtype, no memory), as _Fpl.backward does; the producer recognises its storage
+            marker = torch.zeros(1, device=dev, dtype=skip.dtype)
+            ctx.skip0.recipes.append((marker, dl, wb, nc))
+            dskip = marker.expand(skip.shape)
+        else:
+            dskip = torch.empty_like(skip)
+            lib.conv2d_dgrad(dl, wb, dskip, N_, Ho, Wo, 32, nc, 1, 1, 0, 0, F32_, BF_)
         params = ctx.params
         with _wgrad_stream(_slot_written(*params), y, skip, dl, dz, wa, wb):
             dwa, dwb = ZERO.get((nc, 32), torch.float32, dev), ZERO.get((nc, 32), torch.float32, dev)
@@ -1512,6 +1529,9 @@ class _UpSkipConvT32AuxLow(_FastFunction):
 
 HEAD_UPADD = True       # False: the resized low-resolution product is added by its own pass (A/B timing)
 TAIL_AUX_LOW = True   # False: the composed head reads the resized 32-channel tensor (the first round-4 form; A/B timing)
+# True: the composed head hands the gradient of its skip input to the BatchNorm + pool node that produced it as (dl, Wb) and that node's two backward kernels
+# form Wb^T dl on load (tcct_bn_pool_bwd_lowrank): the conv2d_dgrad launch and the 32-channel gradient it wrote are gone.  False: the dense tensor (A/B timing)
+SKIP0_LOWRANK = True
 
 
 def up_skip_conv_t32_aux_low(y, skip, w1, b1, w2, b2, w3, b3, align_corners=True):
@@ -2234,17 +2254,37 @@ def pw_conv_bn(x, w, bias, bn, post_act=None, residual=None, fork=False, x2=None
 BN_POOL_FUSE = True      # False: BatchNorm pass, then the pooling pass (A/B timing)
 
 
+class Skip0Link:
+    """Travels with the full-size output z of a _BnPoolFork node (`z._skip0`).  A consumer whose gradient of z is a low-rank product -- the composed level-0
+    head, d loss / dz = Wb^T dl -- files (marker, dl, wb, n_class) in `recipes` and returns the zero-stride placeholder `marker.expand(z.shape)` to autograd;
+    the node's backward runs tcct_bn_pool_bwd_lowrank when that single placeholder is all it received, and materialises the recipes when autograd had to add
+    the placeholder to another consumer's gradient.  ok: the node's shape / kinds have the low-rank kernels (bn_pool_lowrank_ok).
+    The head decides when it runs and clears stale recipes first (DESIGN 3a-9 has the reasoning).
+    LIMITATION (as grad_is_watched documents for the feature-polarization loss): `torch.autograd.grad(loss, z)` and a hook put on z after the head ran see the
+    all-zero placeholder, not Wb^T dl; a z that is hooked or retains its gradient when the head runs takes the dense path."""
+    __slots__ = ('ok', 'recipes')
+
+    def __init__(self, ok):
+        self.ok, self.recipes = bool(ok), []
+
+
+def bn_pool_lowrank_ok(x, pre, post):
+    """tcct_bn_pool_bwd_lowrank's own test: bf16, 32 channels, LeakyReLU in front and nothing behind (the CNN encoder's level 0)"""
+    return x.dtype == torch.bfloat16 and x.shape[-1] == 32 and pre == ACT['lrelu'] and post == ACT['none']
+
+
 class _BnPoolFork(_FastFunction):
     """(maxpool2(z), z) with z = post(BN_train(pre(x))) from ONE pass over x (tcct_bn_pool_fwd_train); in the backward pass the gradient of
     z -- the skip consumers' gradient plus the pooling scatter -- is never written: both BatchNorm backward kernels rebuild it from its
     two sources (tcct_bn_pool_bwd).  Encoder levels 0-3 (reference nets/tcct.py:820-823, :876-884)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, rm, rv, nbt, eps, momentum, pre, post):
+    def forward(ctx, x, gamma, beta, rm, rv, nbt, eps, momentum, pre, post, link=None):
         ctx.set_materialize_grads(False)
         _chk(x, gamma, beta)
         N, H, W, C = x.shape
         dc = dtype_code(x.dtype)
+        ctx.link = link
         fused = getattr(x, '_bn_sums', None)
         if fused is not None and fused[1] == pre and fused[0].numel() == 2 * C:
             sums = fused[0]
@@ -2268,7 +2308,20 @@ class _BnPoolFork(_FastFunction):
         N, H, W, C = x.shape
         dc = dtype_code(x.dtype)
         if dpool is None and dskip is None:
-            return (None,) * 10
+            return (None,) * 11
+        recipes = []
+        if ctx.link is not None:        # (dl, wb) recipes the composed head filed instead of a dense gradient of z (SKIP0_LOWRANK)
+            recipes, ctx.link.recipes = ctx.link.recipes, []
+        lowrank = None
+        if len(recipes) == 1 and dskip is not None and dskip.dim() == 4 and dskip.stride(0) == 0 and dskip.data_ptr() == recipes[0][0].data_ptr():
+            lowrank, dskip = recipes[0], None       # the single placeholder, untouched by autograd
+        elif recipes:
+            # autograd ADDED the placeholder(s) to another consumer's gradient (or to each other): the dense sum lacks the heads' part -- materialise it
+            dskip = None if dskip is None else _as(dskip, x.dtype)
+            for _, dl, wb, nc in recipes:
+                d = torch.empty_like(x)
+                lib.conv2d_dgrad(dl, wb, d, N, H, W, C, nc, 1, 1, 0, 0, dtype_code(torch.float32), dc)
+                dskip = d if dskip is None else add(dskip, d)
         if dpool is None:           # only the full-size output was used: a plain BatchNorm backward
             dpool = torch.zeros((N, H // 2, W // 2, C), device=x.device, dtype=x.dtype)      # an INPUT of the kernel: must really be zero
         dpool = _as(dpool, x.dtype)
@@ -2278,8 +2331,13 @@ class _BnPoolFork(_FastFunction):
         dx = torch.empty_like(x)
         dg = _grad_out(gamma) if ZERO.active and getattr(gamma, '_grad_slot', None) is not None else torch.empty(C, device=x.device, dtype=torch.float32)
         db = _grad_out(beta) if ZERO.active and getattr(beta, '_grad_slot', None) is not None else torch.empty(C, device=x.device, dtype=torch.float32)
-        lib.bn_pool_bwd(x, dpool, dskip, amax, dx, N, H, W, C, mean_rstd, ab, pre, post, sums, dg, db, dc)
-        return dx, _ret(dg, gamma), _ret(db, beta), None, None, None, None, None, None, None
+        if lowrank is not None:
+            _, dl, wb, nc = lowrank
+            keep_until_end_of_step(dl, wb, torch.cuda.current_stream())     # handed over beside autograd: nothing else ties their lifetime to this stream
+            lib.bn_pool_bwd_lowrank(x, dpool, dl, wb, nc, amax, dx, N, H, W, C, mean_rstd, ab, pre, post, sums, dg, db, dc)
+        else:
+            lib.bn_pool_bwd(x, dpool, dskip, amax, dx, N, H, W, C, mean_rstd, ab, pre, post, sums, dg, db, dc)
+        return dx, _ret(dg, gamma), _ret(db, beta), None, None, None, None, None, None, None, None
 
 
 def bn_pool_ok(x, training):
@@ -2292,7 +2350,10 @@ def bn_pool_ok(x, training):
 def batchnorm_maxpool2_fork(x, gamma, beta, running_mean, running_var, num_batches_tracked=None, eps=1e-5, momentum=0.1, pre_act=None,
                             post_act=None):
     """(maxpool2(z), z), z = post_act(BN_train(pre_act(x))): see _BnPoolFork; check bn_pool_ok(x, training) first"""
-    return _BnPoolFork.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, float(eps), float(momentum), ACT[pre_act], ACT[post_act])
+    link = Skip0Link(bn_pool_lowrank_ok(x, ACT[pre_act], ACT[post_act]))
+    pooled, z = _BnPoolFork.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, float(eps), float(momentum), ACT[pre_act], ACT[post_act], link)
+    z._skip0 = link         # what the composed level-0 head (_UpSkipConvT32AuxLow) looks for on its skip input
+    return pooled, z
 
 
 def batchnorm(x, gamma, beta, running_mean, running_var, num_batches_tracked=None, eps=1e-5, momentum=0.1,
