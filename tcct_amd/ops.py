@@ -311,6 +311,12 @@ def _grad_out(param, shape=None):
     return ZERO.get(tuple(shape if shape is not None else param.shape), torch.float32, param.device)
 
 
+def _written_grad_out(param, n):
+    """destination of a parameter gradient [n] that the kernel WRITES (the BatchNorm family's dgamma / dbeta): the parameter's slot, else an uninitialised
+    tensor.  Not _grad_out: its fallback is a zeroed pool tensor, for kernels that accumulate -- here that would spend pool space on zeros nobody reads."""
+    return _grad_out(param) if ZERO.active and getattr(param, '_grad_slot', None) is not None else torch.empty(n, device=param.device, dtype=torch.float32)
+
+
 def _zeros(shape, dtype, device):
     """a zero-filled accumulation output: out of the step's pre-zeroed pool when one is active"""
     return ZERO.get(shape, dtype, device) if ZERO.active else torch.zeros(shape, device=device, dtype=dtype)
@@ -494,6 +500,18 @@ def _stat_sums(stats_box, C, device):
         return None, 0
     stats_box[1] = _zeros((2 * C,), torch.float64, device)
     return stats_box[1], stats_box[0]
+
+
+def _stats_box(stats_pre):
+    """[pre-activation code, None] for a node whose kernel may accumulate the statistics of the train-mode BatchNorm behind it (slot 1 receives them), or None"""
+    return [ACT[stats_pre], None] if stats_pre is not None else None
+
+
+def _tag_bn_sums(y, box):
+    """the node filled its box: y carries (sums, pre-activation code) as `_bn_sums`, which _bn_batch_sums takes instead of running tcct_bn_stats"""
+    if box is not None and box[1] is not None:
+        y._bn_sums = (box[1], box[0])
+    return y
 
 
 def _clear_unless_prezeroed(dw, db):
@@ -730,11 +748,9 @@ def conv2d_fork(x, w, bias=None, stride=1, pad=0, stats_pre=None):
     ph, pw = (pad, pad) if isinstance(pad, int) else pad
     if not (torch.is_grad_enabled() and x.requires_grad and x.dim() == 4):
         return conv2d(x, w, bias, stride, pad, stats_pre=stats_pre), x
-    box = [ACT[stats_pre], None] if stats_pre is not None else None
+    box = _stats_box(stats_pre)
     y, alias = _Conv2d.apply(x, w, bias, stride, ph, pw, None, box, True)
-    if box is not None and box[1] is not None:
-        y._bn_sums = (box[1], box[0])
-    return y, alias
+    return _tag_bn_sums(y, box), alias
 
 
 def conv2d(x, w, bias=None, stride=1, pad=0, out_dtype=None, stats_pre=None):
@@ -747,13 +763,11 @@ def conv2d(x, w, bias=None, stride=1, pad=0, out_dtype=None, stats_pre=None):
         x = x.unsqueeze(2)
     if w.dim() == 2:
         w = w.view(w.shape[0], w.shape[1], 1, 1)
-    box = [ACT[stats_pre], None] if stats_pre is not None else None
+    box = _stats_box(stats_pre)
     y = _Conv2d.apply(x, w, bias, stride, ph, pw, out_dtype, box, False)
     if tok:
         y = y.squeeze(2)
-    if box is not None and box[1] is not None:
-        y._bn_sums = (box[1], box[0])
-    return y
+    return _tag_bn_sums(y, box)
 
 
 # ---- conv3x3 -> conv3x3 with nothing between them as ONE launch each way (round 5, csrc/conv_chain.hip) ---------------------------------------
@@ -856,13 +870,12 @@ def conv3x3_chain(x, w1, b1, w2, b2, stats_pre=None, fork=False):
     gradient is then added inside the input-gradient chain's epilogue."""
     if stats_pre not in (None, 'lrelu'):
         raise TcctError('conv3x3_chain: fused statistics only behind LeakyReLU')
-    box = [ACT[stats_pre], None] if stats_pre is not None else None
+    box = _stats_box(stats_pre)
     if fork and x.requires_grad:
         y, alias = _ConvChain33.apply(x, w1, b1, w2, b2, box, True)
     else:
         y, alias = _ConvChain33.apply(x, w1, b1, w2, b2, box, False), x
-    if box is not None and box[1] is not None:
-        y._bn_sums = (box[1], box[0])
+    _tag_bn_sums(y, box)
     return (y, alias) if fork else y
 
 
@@ -1508,11 +1521,8 @@ class _UpSkipConvT32AuxLow(_FastFunction):
         dy = torch.empty_like(y)
         lib.conv2d_dgrad(dz, wa, dy, N_, H, W_, 32, nc, 1, 1, 0, 0, F32_, BF_)
         if ctx.skip0 is not None:
-            # d loss / d skip = Wb^T dl has rank n_class: the producer's backward kernels form it on load from (dl, wb).  What autograd carries is a
-            # zero-stride expansion of one zero element (right shape and dtype, no memory), as _Fpl.backward does; the producer recognises its storage
-            marker = torch.zeros(1, device=dev, dtype=skip.dtype)
-            ctx.skip0.recipes.append((marker, dl, wb, nc))
-            dskip = marker.expand(skip.shape)
+            # d loss / d skip = Wb^T dl has rank n_class: the producer's backward kernels form it on load from (dl, wb); autograd carries the placeholder
+            dskip = ctx.skip0.file((dl, wb, nc), skip.shape, skip.dtype, dev)
         else:
             dskip = torch.empty_like(skip)
             lib.conv2d_dgrad(dl, wb, dskip, N_, Ho, Wo, 32, nc, 1, 1, 0, 0, F32_, BF_)
@@ -1692,11 +1702,8 @@ def conv1x1_cat2(a, b, w, stats_pre=None):
           and Cout % 32 == 0 and Cout <= 160 and tuple(w.shape[1:]) == (Ca + Cb, 1, 1) and a.dim() == 4)
     if not ok:
         return conv2d(concat2(a, b), w, None, stats_pre=stats_pre)
-    box = [ACT[stats_pre], None] if stats_pre is not None else None
-    y = _PwCat2.apply(a, b, w, box)
-    if box is not None and box[1] is not None:
-        y._bn_sums = (box[1], box[0])
-    return y
+    box = _stats_box(stats_pre)
+    return _tag_bn_sums(_PwCat2.apply(a, b, w, box), box)
 
 
 def im2col3x3_c3(x4, stride=1):
@@ -1771,11 +1778,8 @@ def conv3x3_c3(x4, w, bias, stride=1, stats_pre=None, infer_bn=None, post_act=No
             else:
                 lib.c3_fwd(x4, w, bias, y, B, H, W, stride, None, 0, ab, 0, ACT[post_act])
             return y
-        box = [ACT[stats_pre], None] if stats_pre is not None else None
-        y = _ConvC3.apply(x4, w, bias, stride, box)
-        if box is not None and box[1] is not None:
-            y._bn_sums = (box[1], box[0])
-        return y
+        box = _stats_box(stats_pre)
+        return _tag_bn_sums(_ConvC3.apply(x4, w, bias, stride, box), box)
     w2 = torch.nn.functional.pad(w.permute(0, 2, 3, 1).reshape(w.shape[0], 27), (0, 5)).contiguous()
     if infer_bn is not None:
         return conv_bn_act(im2col3x3_c3(x4, stride), w2.view(w.shape[0], 32, 1, 1), bias, bn=infer_bn, post_act=post_act)
@@ -1798,8 +1802,7 @@ class _ConvC3BN(_FastFunction):
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         z = torch.empty((B, Ho, Wo, 32), device=x4.device, dtype=torch.bfloat16)
         sums = _zeros((64,), torch.float64, x4.device)
-        mean_rstd = torch.empty(64, device=x4.device, dtype=torch.float32)
-        ab = torch.empty(64, device=x4.device, dtype=torch.float32)
+        mean_rstd, ab = _bn_coef_bufs(32, x4.device)
         lib.c3_bn_fwd_train(x4, w, bias, z, B, H, W, stride, sums, gamma, beta, eps, momentum, rm, rv, nbt, mean_rstd, ab, post)
         ctx.save_for_backward(x4, mean_rstd, ab)
         ctx.cfg = (stride, post, w, bias, gamma, beta)
@@ -1817,8 +1820,7 @@ class _ConvC3BN(_FastFunction):
         coef = torch.empty(160, device=dev, dtype=torch.float32)
         # nothing downstream waits for this node (the image has no gradient): all of it runs beside the other encoder's tail on the weight-gradient stream
         with _wgrad_stream(_slot_written(w, bias, gamma, beta), x4, dz, coef, mean_rstd, ab):
-            dg = _grad_out(gamma) if ZERO.active and getattr(gamma, '_grad_slot', None) is not None else torch.empty(32, device=dev, dtype=torch.float32)
-            db_ = _grad_out(beta) if ZERO.active and getattr(beta, '_grad_slot', None) is not None else torch.empty(32, device=dev, dtype=torch.float32)
+            dg, db_ = _written_grad_out(gamma, 32), _written_grad_out(beta, 32)
             dw = _grad_out(w, tuple(w.shape))
             dbias = _grad_out(bias) if bias is not None else None
             if C3_ONEPASS:      # reduction and weight gradient from ONE pass over dz (the BatchNorm backward is linear in per-pixel quantities)
@@ -1856,7 +1858,7 @@ class _DwConv(_FastFunction):
     @staticmethod
     def forward(ctx, x, w, bias, stride, add_input, fork=False, stats_box=None, xab=None, xlink=None):
         """fork: also return an alias of x for its other consumers; their gradient is added inside the input-gradient kernel.
-        stats_box ([None]): the kernel also accumulates the statistics of the train-mode BatchNorm that consumes the output.
+        stats_box (_stats_box('none')): the kernel also accumulates the statistics of the train-mode BatchNorm that consumes the output.
         xab (round 4): x is y_prev, the input of a train-mode BatchNorm + Hardswish in front whose normalisation pass was not run (xab = its {a[C], b[C]});
         the kernels apply z = hswish(a y_prev + b) as rows enter their register window.  The gradient returned for x is the gradient of that z."""
         ctx.set_materialize_grads(False)      # an unused output must arrive as None in backward(), not as a zero-filled tensor
@@ -1871,13 +1873,11 @@ class _DwConv(_FastFunction):
                 raise TcctError('dwconv3x3(deferred=...): plain convolution with C % 4 == 0, C <= 256 only')
             sums = None
             if stats_box is not None:
-                sums = _zeros((2 * C,), torch.float64, x.device)
-                stats_box[0] = sums
+                sums = stats_box[1] = _zeros((2 * C,), torch.float64, x.device)
             lib.dwconv3x3_fwd_xaff(x, xab, w, bias, y, N, H, W, C, stride, sums, dtype_code(x.dtype))
         elif stats_box is not None and C % 4 == 0 and C <= 256:
-            sums = _zeros((2 * C,), torch.float64, x.device)
+            sums = stats_box[1] = _zeros((2 * C,), torch.float64, x.device)
             lib.dwconv3x3_fwd_bnstats(x, w, bias, y, N, H, W, C, stride, int(add_input), sums, dtype_code(x.dtype))
-            stats_box[0] = sums
         else:
             lib.dwconv3x3_fwd(x, w, bias, y, N, H, W, C, stride, int(add_input), dtype_code(x.dtype))
         ctx.save_for_backward(x, w)
@@ -1923,13 +1923,8 @@ def dwconv3x3(x, w, bias=None, stride=1, add_input=False, bn_stats=False, deferr
     """bn_stats: a train-mode BatchNorm (no activation in front) consumes the output: its statistics come out of the same launch (`_bn_sums`).
     deferred: the BnLink of a BatchNorm + Hardswish whose normalisation is pending on x (batchnorm_deferred / pw_conv_bn(defer_apply=True))"""
     xab = deferred.ab if deferred is not None else None
-    if bn_stats:
-        box = [None]
-        y = _DwConv.apply(x, w, bias, stride, add_input, False, box, xab, deferred)
-        if box[0] is not None:
-            y._bn_sums = (box[0], ACT['none'])
-        return y
-    return _DwConv.apply(x, w, bias, stride, add_input, False, None, xab, deferred)
+    box = _stats_box('none') if bn_stats else None
+    return _tag_bn_sums(_DwConv.apply(x, w, bias, stride, add_input, False, box, xab, deferred), box)
 
 
 def dwconv3x3_fork(x, w, bias=None, stride=1, add_input=False):
@@ -1940,6 +1935,44 @@ def dwconv3x3_fork(x, w, bias=None, stride=1, add_input=False):
 
 
 # ------------------------------------------------------------------------------------------------- norms
+def _bn_batch_sums(x, pre, C, M, dc):
+    """[sum | sum of squares] (fp64 [2C]) of pre(x) per channel: what the producing convolution's epilogue accumulated (`_bn_sums`, _tag_bn_sums) when it was
+    taken behind the same pre-activation at this width, else one tcct_bn_stats launch (which clears its output itself outside a pooled step)"""
+    fused = getattr(x, '_bn_sums', None)
+    if fused is not None and fused[1] == pre and fused[0].numel() == 2 * C:
+        return fused[0]
+    sums = ZERO.get((2 * C,), torch.float64, x.device)
+    lib.bn_stats(x, M, C, pre, sums, dc)
+    return sums
+
+
+def _bn_coef_bufs(C, device):
+    """(mean_rstd, ab): {mean[C], rstd[C]} and {a[C], b[C]} of y = a x + b, written by the launch that finalises the statistics and kept for the backward"""
+    return torch.empty(2 * C, device=device, dtype=torch.float32), torch.empty(2 * C, device=device, dtype=torch.float32)
+
+
+def _bn_backward(ctx, dy):
+    """-> (dx, dgamma, dbeta) of a train-mode BatchNorm node that saved (x, gamma, mean_rstd, ab) and set cfg = (pre, post), beta_param, link"""
+    x, gamma, mean_rstd, ab = ctx.saved_tensors
+    pre, post = ctx.cfg
+    dy = _as(dy, x.dtype)
+    C = x.shape[-1]
+    M = x.numel() // C
+    dc = dtype_code(x.dtype)
+    link = ctx.link
+    if link is not None and link.sums is not None:      # the consumer's input-gradient kernel accumulated the two batch sums (raw form)
+        sums = torch.empty(2 * C, device=x.device, dtype=torch.float64)
+        lib.bn_sums_from_raw(link.sums, mean_rstd, C, sums)
+        link.sums = None
+    else:
+        sums = ZERO.get((2 * C,), torch.float64, x.device)
+        lib.bn_bwd_reduce(x, dy, M, C, mean_rstd, ab, pre, post, sums, dc)
+    dx = torch.empty_like(x)
+    dg, db = _written_grad_out(gamma, C), _written_grad_out(ctx.beta_param, C)
+    lib.bn_bwd_apply(x, dy, dx, M, C, mean_rstd, ab, gamma, sums, pre, post, dg, db, dc)
+    return dx, _ret(dg, gamma), _ret(db, ctx.beta_param)
+
+
 class _BatchNorm(_FastFunction):
     @staticmethod
     def forward(ctx, x, gamma, beta, rm, rv, nbt, eps, momentum, pre, post, training, res=None, link=None):
@@ -1947,15 +1980,9 @@ class _BatchNorm(_FastFunction):
         C = x.shape[-1]
         M = x.numel() // C
         dc = dtype_code(x.dtype)
-        mean_rstd = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-        ab = torch.empty(2 * C, device=x.device, dtype=torch.float32)
+        mean_rstd, ab = _bn_coef_bufs(C, x.device)
         if training:
-            fused = getattr(x, '_bn_sums', None)
-            if fused is not None and fused[1] == pre and fused[0].numel() == 2 * C:
-                sums = fused[0]             # statistics were accumulated by the producing conv's epilogue
-            else:
-                sums = ZERO.get((2 * C,), torch.float64, x.device)
-                lib.bn_stats(x, M, C, pre, sums, dc)
+            sums = _bn_batch_sums(x, pre, C, M, dc)
         else:
             lib.bn_eval_ab(C, gamma, beta, eps, rm, rv, mean_rstd, ab)
         y = torch.empty_like(x)
@@ -1981,25 +2008,9 @@ class _BatchNorm(_FastFunction):
 
     @staticmethod
     def backward(ctx, dy):
-        x, gamma, mean_rstd, ab = ctx.saved_tensors
-        pre, post = ctx.cfg
-        dy = _as(dy, x.dtype)
-        C = x.shape[-1]
-        M = x.numel() // C
-        dc = dtype_code(x.dtype)
-        link = getattr(ctx, 'link', None)
-        if link is not None and link.sums is not None:      # the consumer's input-gradient kernel accumulated the two batch sums (raw form)
-            sums = torch.empty(2 * C, device=x.device, dtype=torch.float64)
-            lib.bn_sums_from_raw(link.sums, mean_rstd, C, sums)
-            link.sums = None
-        else:
-            sums = ZERO.get((2 * C,), torch.float64, x.device)
-            lib.bn_bwd_reduce(x, dy, M, C, mean_rstd, ab, pre, post, sums, dc)
-        dx = torch.empty_like(x)
-        dg = _grad_out(gamma) if ZERO.active and getattr(gamma, '_grad_slot', None) is not None else torch.empty(C, device=x.device, dtype=torch.float32)
-        db = _grad_out(ctx.beta_param) if ZERO.active and getattr(ctx.beta_param, '_grad_slot', None) is not None else torch.empty(C, device=x.device, dtype=torch.float32)
-        lib.bn_bwd_apply(x, dy, dx, M, C, mean_rstd, ab, gamma, sums, pre, post, dg, db, dc)
-        return dx, _ret(dg, gamma), _ret(db, ctx.beta_param), None, None, None, None, None, None, None, None, (dy if ctx.has_res else None), None
+        if ctx.has_res:         # the residual receives the gradient as the kernels read it
+            dy = _as(dy, ctx.saved_tensors[0].dtype)
+        return _bn_backward(ctx, dy) + (None, None, None, None, None, None, None, None, (dy if ctx.has_res else None), None)
 
 
 # ---- BatchNorm backward folded into the neighbouring pointwise-convolution kernels (round 3) ------------------------------------------
@@ -2055,8 +2066,7 @@ class _PwConvBN(_FastFunction):
             lib.pw_fwd_cat2(x, x2, K1, w, bias, y, M, K, N, sums, 0)
         else:
             lib.pw_fwd_bnstats(x, w, bias, y, M, K, N, sums, 0)
-        mean_rstd = torch.empty(2 * N, device=x.device, dtype=torch.float32)
-        ab = torch.empty(2 * N, device=x.device, dtype=torch.float32)
+        mean_rstd, ab = _bn_coef_bufs(N, x.device)
         if defer_apply:     # round 4: the normalisation pass is left to the one consumer (a depthwise convolution built with `deferred=link`): z is never written
             lib.bn_finalize(sums, M, N, gamma, beta, eps, momentum, rm, rv, nbt, mean_rstd, ab)
             z = y.view_as(y)
@@ -2083,8 +2093,7 @@ class _PwConvBN(_FastFunction):
         else:
             sums, raw = ZERO.get((2 * N,), torch.float64, y.device), 0
             lib.bn_bwd_reduce(y, dz, M, N, mean_rstd, ab, 0, post, sums, dtype_code(y.dtype))
-        dg = _grad_out(gamma) if ZERO.active and getattr(gamma, '_grad_slot', None) is not None else torch.empty(N, device=y.device, dtype=torch.float32)
-        db_ = _grad_out(beta) if ZERO.active and getattr(beta, '_grad_slot', None) is not None else torch.empty(N, device=y.device, dtype=torch.float32)
+        dg, db_ = _written_grad_out(gamma, N), _written_grad_out(beta, N)
         dx = torch.empty_like(x)
         dx2 = torch.empty_like(x2) if x2 is not None else None
         dw = _grad_out(wsrc, tuple(w.shape))
@@ -2163,32 +2172,19 @@ class _BatchNormDeferred(_FastFunction):
         _chk(x, gamma, beta)
         C = x.shape[-1]
         M = x.numel() // C
-        fused = getattr(x, '_bn_sums', None)
-        if fused is not None and fused[1] == 0 and fused[0].numel() == 2 * C:
-            sums = fused[0]
-        else:
-            sums = _zeros((2 * C,), torch.float64, x.device)
-            lib.bn_stats(x, M, C, 0, sums, dtype_code(x.dtype))
-        mean_rstd = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-        ab = torch.empty(2 * C, device=x.device, dtype=torch.float32)
+        sums = _bn_batch_sums(x, 0, C, M, dtype_code(x.dtype))
+        mean_rstd, ab = _bn_coef_bufs(C, x.device)
         lib.bn_finalize(sums, M, C, gamma, beta, eps, momentum, rm, rv, nbt, mean_rstd, ab)
         ctx.save_for_backward(x, gamma, mean_rstd, ab)
         ctx.cfg = (0, post)
         ctx.beta_param = beta
-        ctx.has_res = False
         ctx.link = link
         link.y, link.ab = x, ab
         return x.view_as(x)
 
-    backward = None     # assigned below: _BatchNorm.backward with its return tuple cut to this node's inputs
-
-
-def _bn_deferred_backward(ctx, dy):
-    out = _BatchNorm.backward(ctx, dy)
-    return out[0], out[1], out[2], None, None, None, None, None, None, None
-
-
-_BatchNormDeferred.backward = staticmethod(_bn_deferred_backward)
+    @staticmethod
+    def backward(ctx, dy):
+        return _bn_backward(ctx, dy) + (None,) * 7
 
 
 def batchnorm_deferred_ok(x, bn_training, post_act):
@@ -2254,18 +2250,74 @@ def pw_conv_bn(x, w, bias, bn, post_act=None, residual=None, fork=False, x2=None
 BN_POOL_FUSE = True      # False: BatchNorm pass, then the pooling pass (A/B timing)
 
 
-class Skip0Link:
-    """Travels with the full-size output z of a _BnPoolFork node (`z._skip0`).  A consumer whose gradient of z is a low-rank product -- the composed level-0
-    head, d loss / dz = Wb^T dl -- files (marker, dl, wb, n_class) in `recipes` and returns the zero-stride placeholder `marker.expand(z.shape)` to autograd;
-    the node's backward runs tcct_bn_pool_bwd_lowrank when that single placeholder is all it received, and materialises the recipes when autograd had to add
-    the placeholder to another consumer's gradient.  ok: the node's shape / kinds have the low-rank kernels (bn_pool_lowrank_ok).
-    The head decides when it runs and clears stale recipes first (DESIGN 3a-9 has the reasoning).
-    LIMITATION (as grad_is_watched documents for the feature-polarization loss): `torch.autograd.grad(loss, z)` and a hook put on z after the head ran see the
-    all-zero placeholder, not Wb^T dl; a z that is hooked or retains its gradient when the head runs takes the dense path."""
-    __slots__ = ('ok', 'recipes')
+class LazyGrad:
+    """A gradient that travels beside autograd as a RECIPE, and the only place that knows what its placeholder is.  One link per forward node of a PRODUCER
+    whose backward kernels can form the gradient of its output t on load (_NormAdd / _NormAdd6: `feats`; _BnPoolFork: the level-0 skip z); the producer's ctx
+    owns it.  A CONSUMER whose d loss / dt is cheap to describe (_Fpl: a (labels, bins, table) lookup; the composed level-0 head: Wb^T dl, rank n_class) calls
+    `file` in its backward and returns the placeholder -- a zero-stride expansion of one zero element: right shape and dtype, no memory -- to autograd.  The
+    producer's backward calls `take(dy)`: the single untouched placeholder means its fused kernels run on the recipe; a placeholder that autograd ADDED to
+    another consumer's gradient (or to another placeholder) arrives as a dense tensor that lacks the filed parts, and every recipe has to be materialised and
+    added (_add_materialised).  ok: the producer has the fused kernels for its shape / kinds.
 
-    def __init__(self, ok):
+    How a consumer finds the link: the skip edge carries it as a tensor attribute (`z._skip0`, forwarded by grad_mark); `feats` reaches RegNet.regular_udh as
+    an NCHW view of a view through the reference's public `base.feats` protocol, which attributes do not survive, so _NormAdd / _NormAdd6 `register` their
+    output's address for the step and _Fpl looks it up (`of`); begin_step resets the registry, and an entry is void once the producer's node is gone.
+    HAZARD: the registry cannot tell a registered tensor from a later one that the allocator put at the same address while the producer's node is still
+    alive (its output freed, an alias of its inputs still held) -- a recipe filed on such a tensor would reach that producer's link and be lost to the
+    tensor's real one.  Nothing here detects it; FTC keeps `feats` alive until the next forward pass (`_feats`), so a training step does not meet it.
+    LIMITATION (only what exists when the consumer's forward runs is visible to grad_is_watched): `torch.autograd.grad(loss, t)` and a hook registered on t
+    AFTER the consumer ran receive the all-zero placeholder; the real gradient still reaches every weight.  A caller who wants to SEE the dense d loss / dt
+    calls `t.retain_grad()` / registers the hook BEFORE the consumer runs (RegNet.regular_udh, the head), or `ops.fpl(..., allow_lazy=False)`, or clears
+    `ops.FPL_LAZY_GRAD` / `ops.SKIP0_LOWRANK`."""
+    __slots__ = ('ok', 'recipes', '__weakref__')
+    _by_address = {}        # data_ptr of a registered producer output -> weak reference to its link, for the running step
+
+    def __init__(self, ok=True):
         self.ok, self.recipes = bool(ok), []
+
+    def register(self, t):
+        LazyGrad._by_address[t.data_ptr()] = weakref.ref(self)      # weak: the producer's ctx owns the link, an entry dies with the producer's node
+
+    @staticmethod
+    def of(t):
+        ref = LazyGrad._by_address.get(t.data_ptr())
+        return ref() if ref is not None else None
+
+    def file(self, recipe, shape, dtype, device):
+        """consumer side: keep (marker, *recipe) for the producer, -> the placeholder to return to autograd as the gradient"""
+        marker = torch.zeros(1, device=device, dtype=dtype)
+        self.recipes.append((marker,) + tuple(recipe))
+        return marker.expand(shape)
+
+    def take(self, dy):
+        """producer side, dy = what autograd delivered (or None) -> (single, rest) and the link is empty again.  single: the one filed recipe when dy is
+        exactly its untouched placeholder (the caller forms the gradient from it; dy holds nothing); otherwise None, and rest lists the recipes to materialise
+        and add to the dense dy.  Tensor metadata only: no kernel, no library call."""
+        recipes, self.recipes = self.recipes, []
+        if len(recipes) == 1 and dy is not None and dy.dim() == 4 and dy.stride(0) == 0 and dy.data_ptr() == recipes[0][0].data_ptr():
+            return recipes[0], []
+        return None, recipes
+
+
+def fpl_lazy_grad_reset():
+    """per step (begin_step): forget last step's registered producer outputs (storage addresses are recycled by the allocator)"""
+    LazyGrad._by_address.clear()
+
+
+def lazy_grads_pending(*links):
+    """number of recipes filed and not yet taken, on the registered links and on `links` (0 after a complete backward pass)"""
+    live = {ref() for ref in LazyGrad._by_address.values()} - {None}
+    return sum(len(k.recipes) for k in live | set(links))
+
+
+def _add_materialised(dy, recipes, like, materialise):
+    """dy (dense, or None) + every recipe as a tensor like `like`: materialise(recipe, out) launches the consumer's dense gradient kernel, then the sum"""
+    dy = None if dy is None else _as(dy, like.dtype)
+    for recipe in recipes:
+        d = torch.empty_like(like)
+        materialise(recipe, d)
+        dy = d if dy is None else add(dy, d)
+    return dy
 
 
 def bn_pool_lowrank_ok(x, pre, post):
@@ -2285,14 +2337,8 @@ class _BnPoolFork(_FastFunction):
         N, H, W, C = x.shape
         dc = dtype_code(x.dtype)
         ctx.link = link
-        fused = getattr(x, '_bn_sums', None)
-        if fused is not None and fused[1] == pre and fused[0].numel() == 2 * C:
-            sums = fused[0]
-        else:
-            sums = ZERO.get((2 * C,), torch.float64, x.device)
-            lib.bn_stats(x, N * H * W, C, pre, sums, dc)
-        mean_rstd = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-        ab = torch.empty(2 * C, device=x.device, dtype=torch.float32)
+        sums = _bn_batch_sums(x, pre, C, N * H * W, dc)
+        mean_rstd, ab = _bn_coef_bufs(C, x.device)
         z = torch.empty_like(x)
         pooled = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=x.dtype)
         amax = torch.empty((N, H // 2, W // 2, C // 4), device=x.device, dtype=torch.uint8)        # 2-bit window positions of the maxima
@@ -2309,19 +2355,12 @@ class _BnPoolFork(_FastFunction):
         dc = dtype_code(x.dtype)
         if dpool is None and dskip is None:
             return (None,) * 11
-        recipes = []
-        if ctx.link is not None:        # (dl, wb) recipes the composed head filed instead of a dense gradient of z (SKIP0_LOWRANK)
-            recipes, ctx.link.recipes = ctx.link.recipes, []
-        lowrank = None
-        if len(recipes) == 1 and dskip is not None and dskip.dim() == 4 and dskip.stride(0) == 0 and dskip.data_ptr() == recipes[0][0].data_ptr():
-            lowrank, dskip = recipes[0], None       # the single placeholder, untouched by autograd
-        elif recipes:
-            # autograd ADDED the placeholder(s) to another consumer's gradient (or to each other): the dense sum lacks the heads' part -- materialise it
-            dskip = None if dskip is None else _as(dskip, x.dtype)
-            for _, dl, wb, nc in recipes:
-                d = torch.empty_like(x)
-                lib.conv2d_dgrad(dl, wb, d, N, H, W, C, nc, 1, 1, 0, 0, dtype_code(torch.float32), dc)
-                dskip = d if dskip is None else add(dskip, d)
+        # (dl, wb, n_class) recipes the composed head filed instead of a dense gradient of z (SKIP0_LOWRANK)
+        lowrank, rest = ctx.link.take(dskip) if ctx.link is not None else (None, [])
+        if lowrank is not None:
+            dskip = None
+        elif rest:
+            dskip = _add_materialised(dskip, rest, x, lambda r, d: lib.conv2d_dgrad(r[1], r[2], d, N, H, W, C, r[3], 1, 1, 0, 0, dtype_code(torch.float32), dc))
         if dpool is None:           # only the full-size output was used: a plain BatchNorm backward
             dpool = torch.zeros((N, H // 2, W // 2, C), device=x.device, dtype=x.dtype)      # an INPUT of the kernel: must really be zero
         dpool = _as(dpool, x.dtype)
@@ -2329,8 +2368,7 @@ class _BnPoolFork(_FastFunction):
             dskip = _as(dskip, x.dtype)
         sums = ZERO.get((2 * C,), torch.float64, x.device)
         dx = torch.empty_like(x)
-        dg = _grad_out(gamma) if ZERO.active and getattr(gamma, '_grad_slot', None) is not None else torch.empty(C, device=x.device, dtype=torch.float32)
-        db = _grad_out(beta) if ZERO.active and getattr(beta, '_grad_slot', None) is not None else torch.empty(C, device=x.device, dtype=torch.float32)
+        dg, db = _written_grad_out(gamma, C), _written_grad_out(beta, C)
         if lowrank is not None:
             _, dl, wb, nc = lowrank
             keep_until_end_of_step(dl, wb, torch.cuda.current_stream())     # handed over beside autograd: nothing else ties their lifetime to this stream
@@ -2350,7 +2388,7 @@ def bn_pool_ok(x, training):
 def batchnorm_maxpool2_fork(x, gamma, beta, running_mean, running_var, num_batches_tracked=None, eps=1e-5, momentum=0.1, pre_act=None,
                             post_act=None):
     """(maxpool2(z), z), z = post_act(BN_train(pre_act(x))): see _BnPoolFork; check bn_pool_ok(x, training) first"""
-    link = Skip0Link(bn_pool_lowrank_ok(x, ACT[pre_act], ACT[post_act]))
+    link = LazyGrad(bn_pool_lowrank_ok(x, ACT[pre_act], ACT[post_act]))
     pooled, z = _BnPoolFork.apply(x, gamma, beta, running_mean, running_var, num_batches_tracked, float(eps), float(momentum), ACT[pre_act], ACT[post_act], link)
     z._skip0 = link         # what the composed level-0 head (_UpSkipConvT32AuxLow) looks for on its skip input
     return pooled, z
@@ -2382,17 +2420,9 @@ class _Bn2AddAct(_FastFunction):
         M = xa.numel() // C
         dc = dtype_code(xa.dtype)
         st, ss = [], []
-        for x, g, b, (rm, rv, nbt) in ((xa, gA, bA, bufs[0]), (xb, gB, bB, bufs[1])):
-            fused = getattr(x, '_bn_sums', None)
-            if fused is not None and fused[1] == pre and fused[0].numel() == 2 * C:
-                sums = fused[0]
-            else:
-                sums = ZERO.get((2 * C,), torch.float64, x.device)
-                lib.bn_stats(x, M, C, pre, sums, dc)
-            mr = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-            ab = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-            st += [mr, ab]
-            ss.append(sums)
+        for x in (xa, xb):
+            st += _bn_coef_bufs(C, x.device)
+            ss.append(_bn_batch_sums(x, pre, C, M, dc))
         y = torch.empty_like(xa)
         (rmA, rvA, nbtA), (rmB, rvB, nbtB) = bufs       # both statistics finalisations ride on the junction launch
         lib.bn2_add_act_train(xa, xb, y, M, C, ss[0], gA, bA, rmA, rvA, nbtA, st[0], st[1], ss[1], gB, bB, rmB, rvB, nbtB, st[2], st[3],
@@ -2414,10 +2444,7 @@ class _Bn2AddAct(_FastFunction):
         sums = ZERO.get((4 * C,), torch.float64, xa.device)
         lib.bn2_add_act_bwd_reduce(xa, xb, dy, M, C, mrA, abA, mrB, abB, pre, act_kind, sums, dc)
         dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
-        outs = []
-        for p in (gA, bA, gB, bB):
-            use_slot = ZERO.active and getattr(p, '_grad_slot', None) is not None
-            outs.append(_grad_out(p) if use_slot else torch.empty(C, device=xa.device, dtype=torch.float32))
+        outs = [_written_grad_out(p, C) for p in (gA, bA, gB, bB)]
         lib.bn2_add_act_bwd_apply(xa, xb, dy, dxa, dxb, M, C, mrA, abA, mrB, abB, sums, pre, act_kind, outs[0], outs[1], outs[2],
                                   outs[3], dc)
         return (dxa, _ret(outs[0], gA), _ret(outs[1], bA), dxb, _ret(outs[2], gB), _ret(outs[3], bB), None, None, None, None, None)
@@ -3029,22 +3056,17 @@ def l2norm(x, eps=1e-12):
 
 # ---- the feature-polarization gradient without its tensor (round 4) ---------------------------------------------------------------------------
 # regular_udh's d loss / d feats is g * dpro[label[p]][bin[p]] -- a table lookup by two bytes per pixel.  When feats comes out of the fused norm_add
-# node and the FPL is its only differentiable consumer (how FTC / RegNet use it), _Fpl.backward returns a zero-stride placeholder of the right shape
-# and registers (labels, binmap, table, upstream gradient) under the placeholder's storage; _NormAdd.backward picks the recipe up and runs the
-# lookup forms of its three kernels (tcct_l2norm_bwd_fplgrad, tcct_bilinear_bwd_fplgrad): the 452 MB gradient (bench shape) is neither written nor
-# read three times.  A placeholder that autograd had to ADD to another gradient (a second differentiable consumer of feats, the FPL evaluated twice
-# on the same feats) arrives as a dense tensor without the FPL part: every recipe is therefore ALSO filed under its producer (`pending`), and a
-# producer whose incoming gradient is not the single placeholder materialises the pending recipes (tcct_fpl_backward) and adds them.  A feats tensor
-# with hooks / retain_grad (somebody wants to SEE the gradient) never takes the lazy path.  `FPL_LAZY_GRAD = False` (bench.py --set FPL_LAZY_GRAD=0) restores the dense tensor everywhere.
+# node and the FPL is its only differentiable consumer (how FTC / RegNet use it), _Fpl.backward files (labels, binmap, table, upstream gradient, n_class)
+# on the node's LazyGrad link and returns the placeholder; _NormAdd.backward takes the recipe and runs the lookup forms of its three kernels
+# (tcct_l2norm_bwd_fplgrad, tcct_bilinear_bwd_fplgrad): the 452 MB gradient (bench shape) is neither written nor read three times.  With a second
+# differentiable consumer of feats, or the FPL evaluated twice on the same feats, the node materialises the recipes (tcct_fpl_backward) and adds them.  A feats
+# tensor with hooks / retain_grad (somebody wants to SEE the gradient) never takes the lazy path.  `FPL_LAZY_GRAD = False` (bench.py --set FPL_LAZY_GRAD=0) restores the dense tensor everywhere.
 FPL_LAZY_GRAD = True
-_FPL_LAZY = {'producers': set(), 'grads': {}, 'pending': {}}
 
 
-def fpl_lazy_grad_reset():
-    """per step (begin_step): forget last step's registrations (storage addresses are recycled by the allocator)"""
-    _FPL_LAZY['producers'].clear()
-    _FPL_LAZY['grads'].clear()
-    _FPL_LAZY['pending'].clear()
+def _fpl_materialise(dc):
+    """materialise(recipe, out) of _add_materialised for the recipes _Fpl.backward files"""
+    return lambda r, d: lib.fpl_backward(r[1], r[2], r[3], r[4], 1.0, int(r[1].numel()), d, dc)
 
 
 class _NormAdd(_FastFunction):
@@ -3065,74 +3087,60 @@ class _NormAdd(_FastFunction):
         lib.normadd_fwd(g0, g1, g2, inv1, inv2, out, N, H, W, C, h1, w1, h2, w2, eps, dtype_code(g0.dtype))
         ctx.save_for_backward(g0, g1, g2)
         ctx.eps = eps
-        ctx.out_ptr = out.data_ptr()
+        ctx.link = LazyGrad()
         if fork and C == 32:
-            _FPL_LAZY['producers'].add(out.data_ptr())
+            ctx.link.register(out)
         return (out, g0.view_as(g0), g1.view_as(g1), g2.view_as(g2)) if fork else out
 
     @staticmethod
     def backward(ctx, dy, *dalias):
         g0, g1, g2 = ctx.saved_tensors
         dalias = tuple(dalias) + (None,) * (3 - len(dalias))
-        pending = _FPL_LAZY['pending'].pop(ctx.out_ptr, [])        # recipes of every _Fpl node that consumed THIS node's output
-        if dy is None and not pending:          # only the aliases were used downstream
+        lazy, rest = ctx.link.take(dy)          # recipes of every _Fpl node that consumed THIS node's output
+        if dy is None and not rest:             # only the aliases were used downstream
             return dalias[0], dalias[1], dalias[2], None, None
         N, H, W, C = g0.shape
         dc = dtype_code(g0.dtype)
-        lazy = None
-        if dy is not None and len(pending) == 1 and dy.dim() == 4 and dy.stride(0) == 0 and dy.data_ptr() == pending[0][0].data_ptr():
-            lazy = _FPL_LAZY['grads'].pop(dy.data_ptr(), None)     # the single placeholder, untouched by autograd
-        elif pending:
-            # autograd ADDED the placeholder(s) to another gradient (or to each other): the dense sum lacks the FPL part -- materialise it
-            dy = None if dy is None else _c(_as(dy, g0.dtype))
-            for marker, labels, binmap, dpro, gup, ncls in pending:
-                _FPL_LAZY['grads'].pop(marker.data_ptr(), None)
-                dfeat = torch.empty_like(g0)
-                lib.fpl_backward(labels, binmap, dpro, gup, 1.0, int(labels.numel()), dfeat, dc)
-                dy = dfeat if dy is None else add(dy, dfeat)
-        if lazy is not None:    # the gradient is the feature-polarization loss's: looked up, never materialised
+        if lazy is None:
+            dy = _add_materialised(dy, rest, g0, _fpl_materialise(dc))
+        else:                   # the gradient is the feature-polarization loss's: looked up, never materialised
             _, labels, binmap, dpro, gup, ncls = lazy
-            outs = []
-            for g, da in zip((g0, g1, g2), dalias):
-                h, w = g.shape[1], g.shape[2]
-                d = torch.empty_like(g)
-                da = _c(_as(da, g.dtype)) if da is not None else None
-                if (h, w) == (H, W):
-                    lib.l2norm_bwd_fplgrad(g, labels, binmap, dpro, gup, 1.0, ncls, da, d, g.numel() // C, ctx.eps, 1.0 / 3.0, dc)
-                else:
-                    dn = torch.empty_like(g)
-                    lib.bilinear_bwd_fplgrad(labels, binmap, dpro, gup, 1.0, ncls, dn, N, h, w, H, W, 0, dc)
-                    if da is not None:
-                        lib.l2norm_bwd_scaled_add(g, dn, da, d, g.numel() // C, C, ctx.eps, 1.0 / 3.0, dc)
-                    else:
-                        lib.l2norm_bwd_scaled(g, dn, d, g.numel() // C, C, ctx.eps, 1.0 / 3.0, dc)
-                outs.append(d)
-            return outs[0], outs[1], outs[2], None, None
-        dy = _c(_as(dy, g0.dtype))
         outs = []
         for g, da in zip((g0, g1, g2), dalias):
             h, w = g.shape[1], g.shape[2]
-            if (h, w) == (H, W):
-                dn = dy
-            else:
-                dn = torch.empty_like(g)
-                lib.bilinear_bwd(dy, dn, N, h, w, C, H, W, 0, dc)
+            M = g.numel() // C
             d = torch.empty_like(g)
-            if da is not None:
-                lib.l2norm_bwd_scaled_add(g, dn, _c(_as(da, g.dtype)), d, g.numel() // C, C, ctx.eps, 1.0 / 3.0, dc)
+            da = _c(_as(da, g.dtype)) if da is not None else None
+            if lazy is not None and (h, w) == (H, W):
+                lib.l2norm_bwd_fplgrad(g, labels, binmap, dpro, gup, 1.0, ncls, da, d, M, ctx.eps, 1.0 / 3.0, dc)
             else:
-                lib.l2norm_bwd_scaled(g, dn, d, g.numel() // C, C, ctx.eps, 1.0 / 3.0, dc)
+                if (h, w) == (H, W):
+                    dn = dy
+                else:
+                    dn = torch.empty_like(g)
+                    if lazy is not None:
+                        lib.bilinear_bwd_fplgrad(labels, binmap, dpro, gup, 1.0, ncls, dn, N, h, w, H, W, 0, dc)
+                    else:
+                        lib.bilinear_bwd(dy, dn, N, h, w, C, H, W, 0, dc)
+                if da is not None:
+                    lib.l2norm_bwd_scaled_add(g, dn, da, d, M, C, ctx.eps, 1.0 / 3.0, dc)
+                else:
+                    lib.l2norm_bwd_scaled(g, dn, d, M, C, ctx.eps, 1.0 / 3.0, dc)
             outs.append(d)
         return outs[0], outs[1], outs[2], None, None
 
 
-def norm_add3(g0, g1, g2, eps=1e-12):
-    """fused norm_add for three maps with the same channel count (C % 4 == 0, C/4 a power of two <= 64); g1 / g2 coarser than g0"""
+def _norm_add3_ok(g0, g1, g2):
+    """the shapes _NormAdd takes: three NHWC maps of one dtype and channel count (C % 4 == 0, C/4 a power of two <= 64), g1 / g2 not at g0's size"""
     C = g0.shape[-1]
     lp = C // 4
-    ok = (g0.dim() == 4 and g1.shape[-1] == C and g2.shape[-1] == C and C % 4 == 0 and 1 <= lp <= 64 and lp & (lp - 1) == 0
-          and g0.dtype == g1.dtype == g2.dtype and tuple(g1.shape[1:3]) != tuple(g0.shape[1:3]) and tuple(g2.shape[1:3]) != tuple(g0.shape[1:3]))
-    if not ok:
+    return (g0.dim() == 4 and g1.shape[-1] == C and g2.shape[-1] == C and C % 4 == 0 and 1 <= lp <= 64 and lp & (lp - 1) == 0
+            and g0.dtype == g1.dtype == g2.dtype and tuple(g1.shape[1:3]) != tuple(g0.shape[1:3]) and tuple(g2.shape[1:3]) != tuple(g0.shape[1:3]))
+
+
+def norm_add3(g0, g1, g2, eps=1e-12):
+    """fused norm_add for three maps with the same channel count (C % 4 == 0, C/4 a power of two <= 64); g1 / g2 coarser than g0"""
+    if not _norm_add3_ok(g0, g1, g2):
         size = tuple(g0.shape[1:3])
         return add3_scale(l2norm(g0, eps), bilinear(l2norm(g1, eps), size, False), bilinear(l2norm(g2, eps), size, False), 1.0 / 3.0)
     return _NormAdd.apply(g0, g1, g2, float(eps))
@@ -3141,12 +3149,7 @@ def norm_add3(g0, g1, g2, eps=1e-12):
 def norm_add3_fork(g0, g1, g2, eps=1e-12):
     """(norm_add3(g0, g1, g2), g0', g1', g2'): the aliases are to be read by the other consumers of the three maps (the aux heads); returns None
     when the fused form does not apply (the caller then uses norm_add3 and lets autograd accumulate)"""
-    C = g0.shape[-1]
-    lp = C // 4
-    ok = (g0.dim() == 4 and g1.shape[-1] == C and g2.shape[-1] == C and C % 4 == 0 and 1 <= lp <= 64 and lp & (lp - 1) == 0
-          and g0.dtype == g1.dtype == g2.dtype and tuple(g1.shape[1:3]) != tuple(g0.shape[1:3]) and tuple(g2.shape[1:3]) != tuple(g0.shape[1:3])
-          and torch.is_grad_enabled())
-    if not ok:
+    if not (_norm_add3_ok(g0, g1, g2) and torch.is_grad_enabled()):
         return None
     return _NormAdd.apply(g0, g1, g2, float(eps), True)
 
@@ -3169,39 +3172,29 @@ class _NormAdd6(_FastFunction):
         lib.normadd6_fwd(a0, b0, a1, b1, a2, b2, inv1, inv2, out, N, H, W, C, h1, w1, h2, w2, eps, dtype_code(a0.dtype))
         ctx.save_for_backward(a0, b0, a1, b1, a2, b2)
         ctx.eps = eps
-        ctx.out_ptr = out.data_ptr()
-        _FPL_LAZY['producers'].add(out.data_ptr())
+        ctx.link = LazyGrad()
+        ctx.link.register(out)
         return out
 
     @staticmethod
     def backward(ctx, dy):
         xs = ctx.saved_tensors
         a0 = xs[0]
-        pending = _FPL_LAZY['pending'].pop(ctx.out_ptr, [])        # recipes of every _Fpl node that consumed THIS node's output
-        if dy is None and not pending:
+        lazy, rest = ctx.link.take(dy)          # recipes of every _Fpl node that consumed THIS node's output
+        if dy is None and not rest:
             return (None,) * 7
         N, H, W, C = a0.shape
         dc = dtype_code(a0.dtype)
-        lazy = None
-        if dy is not None and len(pending) == 1 and dy.dim() == 4 and dy.stride(0) == 0 and dy.data_ptr() == pending[0][0].data_ptr():
-            lazy = _FPL_LAZY['grads'].pop(dy.data_ptr(), None)     # the single placeholder, untouched by autograd
-        elif pending:
-            # autograd ADDED the placeholder(s) to another gradient (or to each other): the dense sum lacks the FPL part -- materialise it
-            dy = None if dy is None else _c(_as(dy, a0.dtype))
-            for marker, labels, binmap, dpro, gup, ncls in pending:
-                _FPL_LAZY['grads'].pop(marker.data_ptr(), None)
-                dfeat = torch.empty_like(a0)
-                lib.fpl_backward(labels, binmap, dpro, gup, 1.0, int(labels.numel()), dfeat, dc)
-                dy = dfeat if dy is None else add(dy, dfeat)
         if lazy is None:
-            dy = _c(_as(dy, a0.dtype))
+            dy = _add_materialised(dy, rest, a0, _fpl_materialise(dc))
+        else:                   # the gradient is the feature-polarization loss's: looked up, never materialised
+            _, labels, binmap, dpro, gup, ncls = lazy
         outs = []
         for a, b in ((xs[0], xs[1]), (xs[2], xs[3]), (xs[4], xs[5])):
             h, w = a.shape[1], a.shape[2]
             da, db = torch.empty_like(a), torch.empty_like(b)
             M = a.numel() // C
-            if lazy is not None and (h, w) == (H, W):       # the gradient is the feature-polarization loss's: looked up, never materialised
-                _, labels, binmap, dpro, gup, ncls = lazy
+            if lazy is not None and (h, w) == (H, W):
                 lib.l2norm_bwd2_fplgrad(a, b, labels, binmap, dpro, gup, 1.0, ncls, None, None, da, db, M, ctx.eps, 1.0 / 6.0, dc)
             else:
                 if (h, w) == (H, W):
@@ -3209,7 +3202,6 @@ class _NormAdd6(_FastFunction):
                 else:                                       # ONE resize gradient for the pair
                     dn = torch.empty_like(a)
                     if lazy is not None:
-                        _, labels, binmap, dpro, gup, ncls = lazy
                         lib.bilinear_bwd_fplgrad(labels, binmap, dpro, gup, 1.0, ncls, dn, N, h, w, H, W, 0, dc)
                     else:
                         lib.bilinear_bwd(dy, dn, N, h, w, C, H, W, 0, dc)
@@ -3671,9 +3663,8 @@ class _Fpl(_FastFunction):
         lib.fpl_loss(pro_sum, counts, buf_grad, C, pro, loss, dpro)
         ctx.save_for_backward(labels, binmap, dpro)
         ctx.cfg = (feat.shape, feat.dtype, M)
-        # feat is the output of a norm_add node that can look its gradient up from (labels, bins, table) itself (FPL_LAZY_GRAD below)
-        ctx.lazy = (FPL_LAZY_GRAD and allow_lazy and feat.data_ptr() in _FPL_LAZY['producers'] and feat.shape[-1] == 32 and feat.is_contiguous())
-        ctx.producer = feat.data_ptr()
+        # feat is the output of a norm_add node that can look its gradient up from (labels, bins, table) itself (FPL_LAZY_GRAD above): its link, else None
+        ctx.lazy = LazyGrad.of(feat) if (FPL_LAZY_GRAD and allow_lazy and feat.shape[-1] == 32 and feat.is_contiguous()) else None
         ctx.mark_non_differentiable(pro)
         return loss, pro
 
@@ -3684,26 +3675,17 @@ class _Fpl(_FastFunction):
         if g is None:
             return None, None, None, None, None
         g = _as(g, torch.float32)
-        if ctx.lazy:
-            # d loss / d feat is a function of two bytes per pixel: hand norm_add's backward the recipe instead of the 452 MB tensor.  The returned
-            # gradient is a zero-stride expansion of one zero element (right shape and dtype, no memory); the consumer recognises its storage.
-            marker = torch.zeros(1, device=g.device, dtype=dt)
-            recipe = (marker, labels, binmap, dpro, g, int(dpro.shape[0]))
-            _FPL_LAZY['grads'][marker.data_ptr()] = recipe
-            _FPL_LAZY['pending'].setdefault(ctx.producer, []).append(recipe)
-            return marker.expand(shape), None, None, None, None
+        if ctx.lazy is not None:
+            # d loss / d feat is a function of two bytes per pixel: hand norm_add's backward the recipe instead of the 452 MB tensor
+            return ctx.lazy.file((labels, binmap, dpro, g, int(dpro.shape[0])), shape, dt, g.device), None, None, None, None
         dfeat = torch.empty(shape, device=g.device, dtype=dt)
         lib.fpl_backward(labels, binmap, dpro, g, 1.0, M, dfeat, dtype_code(dt))
         return dfeat, None, None, None, None
 
 
 def grad_is_watched(t):
-    """somebody hooks `t` or retains its gradient, i.e. wants to SEE d loss / d t.
-
-    LIMITATION (only what exists when fpl() runs is visible here): `torch.autograd.grad(loss, feats)` and a hook registered on `feats` AFTER the loss was
-    formed are not: inside a pooled training step they receive the zero-stride all-zero PLACEHOLDER of the lazy route (the real gradient travels as a
-    (labels, bins, table) recipe into norm_add's backward kernels and still reaches every weight).  A caller who wants the dense d loss / d feats calls
-    `feats.retain_grad()` / registers the hook BEFORE `RegNet.regular_udh`, or `ops.fpl(..., allow_lazy=False)`, or sets `ops.FPL_LAZY_GRAD = False`."""
+    """somebody hooks `t` or retains its gradient, i.e. wants to SEE d loss / d t: such a tensor never receives a recipe gradient.  Only what exists when the
+    consumer's forward runs is visible here (the LIMITATION in LazyGrad's docstring)."""
     return bool(getattr(t, 'retains_grad', False)) or bool(getattr(t, '_backward_hooks', None))
 
 

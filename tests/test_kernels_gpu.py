@@ -1049,7 +1049,7 @@ def test_fpl_gradient_looked_up_inside_norm_add_backward(cfg):
             aux = sum((a.float() * w_.float()).sum() for a, w_ in zip((a0, a1, a2), wa)) * 1e-3
             (loss * 1.7 + aux).backward()
             res[lazy] = [x.grad.float().cpu() for x in xs]
-            assert not ops._FPL_LAZY['grads']                                           # the recipe was consumed (or never issued)
+            assert ops.lazy_grads_pending() == 0                                        # the recipe was consumed (or never issued)
         finally:
             ops.FPL_LAZY_GRAD = True
     for a, b, nm in zip(res[True], res[False], ('g0', 'g1', 'g2')):
@@ -1097,7 +1097,7 @@ def test_fpl_lazy_gradient_survives_other_consumers_of_feats(case):
             res[lazy] = [x.grad.float().cpu() for x in xs]
             if case == 'retain_grad':
                 fgrad[lazy] = view.grad.float().cpu()
-            assert not ops._FPL_LAZY['grads'] and not ops._FPL_LAZY['pending']
+            assert ops.lazy_grads_pending() == 0
         finally:
             ops.FPL_LAZY_GRAD = True
     for a, b, nm in zip(res[True], res[False], ('g0', 'g1', 'g2')):

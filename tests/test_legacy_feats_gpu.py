@@ -149,7 +149,7 @@ def test_fpl_gradient_looked_up_inside_norm_add6_backward(cfg, second_consumer):
                 total = total + (feats.float() * wside).sum() * 1e-3
             total.backward()
             res[lazy] = [x.grad.float().cpu() for x in xs]
-            assert not ops._FPL_LAZY['grads'] and not ops._FPL_LAZY['pending']          # the recipe was consumed (or never issued)
+            assert ops.lazy_grads_pending() == 0          # the recipe was consumed (or never issued)
         finally:
             ops.FPL_LAZY_GRAD = True
     for a, b, nm in zip(res[True], res[False], ('a0', 'b0', 'a1', 'b1', 'a2', 'b2')):

@@ -191,7 +191,7 @@ def test_watched_z_takes_the_dense_path(watch):
 
 
 def test_nine_classes_fall_back_to_the_dense_path():
-    """n_class = 9 is outside the composed head (ops.up_skip_conv_t32_aux_ok): z -- which still carries its Skip0Link -- feeds the 32-channel tail and a plain
+    """n_class = 9 is outside the composed head (ops.up_skip_conv_t32_aux_ok): z -- which still carries its LazyGrad link -- feeds the 32-channel tail and a plain
     9-class convolution; the node finds no recipe and runs tcct_bn_pool_bwd on the dense gradient.  dx, dgamma, dbeta by tests/test_norm_pool_gpu.py's rule against
     the float64 backward of scatter(gp) + the gradient that reached z (read by a hook)."""
     from tcct_amd import ops, _lib
@@ -218,7 +218,7 @@ def test_nine_classes_fall_back_to_the_dense_path():
         torch.cuda.synchronize()
     finally:
         _lib._TRACE[0] = None
-    assert 'tcct_bn_pool_bwd' in calls and 'tcct_bn_pool_bwd_lowrank' not in calls and z._skip0.recipes == []
+    assert 'tcct_bn_pool_bwd' in calls and 'tcct_bn_pool_bwd_lowrank' not in calls and ops.lazy_grads_pending(z._skip0) == 0
     _, scat, _ = R.maxpool_ref(z.detach().cpu().double(), gp)
     r = R.bn_ref(x, p, 1e-5, 0.1, 'lrelu', 'none', dz_given=(scat.double() + seen[0].cpu().double()).view(-1, 32))
     R.check(xd.grad.view(-1, 32), r['dx'], R.slack_of(r, 'dx', R.K_BNG), 'skip0 nc=9 dx')

@@ -196,13 +196,13 @@ def cases():
     return out
 
 
-def record_cases():
+def record_cases(case_list=None):
     """-> (cases {name: calls}, symbols): every case once as it stands and once inside begin_step / end_step (the pre-zeroed pool; the second pooled step
-    over the same weights, the one recorded, takes its packs out of the step's single pack launch)"""
+    over the same weights, the one recorded, takes its packs out of the step's single pack launch).  case_list: another set of [(name, make)] than cases()"""
     from tcct_amd import ops
     res, symbols = {}, {}
     torch.manual_seed(7)
-    for name, make in cases():
+    for name, make in (cases() if case_list is None else case_list):
         run = make()
         rec = _record(run)
         res[name] = rec.calls
@@ -288,21 +288,23 @@ def digest(calls):
     return {'calls': len(calls), 'per_symbol': dict(sorted(per.items())), 'sha256': hashlib.sha256(canonical(calls).encode()).hexdigest()}
 
 
-def record_steps():
-    """-> {name: calls}: one KiteSeg.train_step (after one warm-up step) and one predict of stc_tt at 2 x 64 x 64 with --los=di+reg+fpl, bf16 and fp32"""
+def record_steps(arms=None):
+    """-> {name: calls}: one KiteSeg.train_step (after one warm-up step) and one predict of stc_tt at 2 x 64 x 64 with --los=di+reg+fpl, bf16 and fp32.
+    arms: [(name, command-line arguments beside the fixed ones)] instead -- bf16 train steps only, named `name`"""
     from tcct_amd.kite.main import parse_args
     from tcct_amd.data import SynthOCT
     from tcct_amd import nets
     from tcct_amd.kite.loop_seg import KiteSeg
     import tempfile
     res = {}
-    for dtype in ('bf16', 'fp32'):
+    for name, argv in arms or [(None, ['--los=di+reg+fpl', f'--dtype={dtype}']) for dtype in ('bf16', 'fp32')]:
         torch.manual_seed(2023)
         torch.cuda.manual_seed_all(2023)
         with tempfile.TemporaryDirectory() as root:
-            args = parse_args(['--los=di+reg+fpl', '--bs=2', '--db=synth', '--pl=false', f'--dtype={dtype}', f'--root={root}'])
+            args = parse_args(argv + ['--bs=2', '--db=synth', '--pl=false', f'--root={root}'])
+            dtype = args.dtype
             ds = SynthOCT(height=64, width=64, device='cuda')
-            net = nets.stc_tt(ds.out_channels, compute_dtype=BF if dtype == 'bf16' else F32)
+            net = nets.stc_tt(ds.out_channels, compute_dtype=BF if dtype == 'bf16' else F32, **(dict(legacy_heads=True) if args.legacy_heads else {}))
             net = nets.RegNet(net, con=args.type_udh, out_channels=ds.out_channels)
             k = KiteSeg(model=net, dataset=ds, root=args.root, args=args)
             k.model.train()
@@ -310,9 +312,10 @@ def record_steps():
             img, lab = img.contiguous(), lab.contiguous()
             k.train_step(img, lab)
             torch.cuda.synchronize()
-            res[f'train_step {dtype}'] = _record(lambda: k.train_step(img, lab)).calls
-            k.model.eval()
-            res[f'predict {dtype}'] = _record(lambda: k.predict(img)).calls
+            res[name or f'train_step {dtype}'] = _record(lambda: k.train_step(img, lab)).calls
+            if name is None:
+                k.model.eval()
+                res[f'predict {dtype}'] = _record(lambda: k.predict(img)).calls
     return res
 
 
@@ -321,20 +324,22 @@ def main():
     p.add_argument('--out', default=FIXTURE)
     p.add_argument('--steps-full', metavar='DIR', default=None, help='also write the full call sequence of every whole step as DIR/<name>.json (one call per line)')
     a = p.parse_args()
-    case_calls, symbols = record_cases()
-    steps = record_steps()
-    if a.steps_full:
-        os.makedirs(a.steps_full, exist_ok=True)
+    write_fixture(a.out, *record_cases(), record_steps(), a.steps_full)
+
+
+def write_fixture(out, case_calls, symbols, steps, steps_full=None):
+    if steps_full:
+        os.makedirs(steps_full, exist_ok=True)
         for name, calls in steps.items():
-            with open(os.path.join(a.steps_full, name.replace(' ', '_') + '.json'), 'w') as f:
+            with open(os.path.join(steps_full, name.replace(' ', '_') + '.json'), 'w') as f:
                 f.write('\n'.join(canonical(c) for c in calls) + '\n')
-    with open(a.out, 'w') as f:
+    with open(out, 'w') as f:
         f.write('{"symbols": {\n' + ',\n'.join(f'{json.dumps(s)}: {json.dumps(n)}' for s, n in sorted(symbols.items())) + '},\n"cases": {\n')
         names = sorted(symbols)
         enc = {n: SAME if n.endswith(' | pooled') and c == case_calls[n[:-len(' | pooled')]] else encode(c, names) for n, c in case_calls.items()}
         f.write(',\n'.join(f'{json.dumps(n)}: {canonical(e)}' for n, e in enc.items()) + '},\n"steps": {\n')
         f.write(',\n'.join(f'{json.dumps(n)}: {json.dumps(digest(c))}' for n, c in steps.items()) + '}}\n')
-    print(f'{a.out}: {len(case_calls)} cases, {sum(len(c) for c in case_calls.values())} calls; steps: '
+    print(f'{out}: {len(case_calls)} cases, {sum(len(c) for c in case_calls.values())} calls; steps: '
           + ', '.join(f'{n} {len(c)}' for n, c in steps.items()))
 
 
