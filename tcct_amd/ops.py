@@ -654,8 +654,9 @@ def _fwd_generic(ctx, x, w, bias, y, stats_box, g):
 
 
 def _dgrad_generic(ctx, dy, w, dskip, dx, g):
-    N, H, W, Cin, _, Cout, KH, KW, _, padh, padw = g
-    lib.conv2d_dgrad(dy, w, dx, N, H, W, Cin, Cout, KH, KW, padh, padw, dtype_code(dy.dtype), dtype_code(dx.dtype))
+    N, _, _, Cin, _, Cout, KH, KW, _, padh, padw = g
+    # the entry takes the extent of its INPUT, dy [N, Ho, Wo, Cout]: the forward's H x W only for 'same' convolutions (an even K, a padded 1x1: Ho != H)
+    lib.conv2d_dgrad(dy, w, dx, N, dy.shape[1], dy.shape[2], Cin, Cout, KH, KW, padh, padw, dtype_code(dy.dtype), dtype_code(dx.dtype))
     return dskip
 
 

@@ -9,12 +9,11 @@ Through tcct_amd.ops where a node exists (the autograd wiring is then covered to
 calls lie between 256-element sentinels with NaN in the body, results of nodes land in allocator blocks that were filled with NaN just before, so an
 unwritten row or a store one past the end shows without any fault.  Not covered: the grid-stride loop of k_l2norm (it needs 2^16 blocks x 256 threads x 4
 = 67 M elements)."""
-import math
-
 import pytest
 import torch
 
 import norm_pool_ref as R
+from gpu_guard import Guard, _poison
 
 pytestmark = pytest.mark.gpu
 
@@ -32,41 +31,6 @@ def _ops():
 def _lib():
     from tcct_amd._lib import lib, TcctError, dtype_code
     return lib, TcctError, dtype_code
-
-
-def _poison(*like):
-    """fill allocator blocks of the sizes about to be handed out with NaN, then free them: an element a kernel leaves unwritten is then NaN, not the
-    previous test's correct value"""
-    for t in like:
-        if t is not None and t.is_floating_point():
-            p = torch.full_like(t, NAN)
-            del p
-
-
-class Guard:
-    """outputs of direct C-ABI calls: each inside a larger buffer with 256 sentinel elements on both sides and NaN in the body"""
-    SENT = 7.0
-
-    def __init__(self):
-        self.items = []
-
-    def new(self, shape, dtype, what):
-        n = math.prod(shape)
-        buf = torch.full((n + 512,), self.SENT, dtype=dtype, device='cuda')
-        body = buf[256:256 + n]
-        if dtype.is_floating_point:
-            body.fill_(NAN)
-        else:
-            body.fill_(85)
-        self.items.append((buf, n, what))
-        return body.view(shape)
-
-    def check(self, nan_ok=()):
-        for buf, n, what in self.items:
-            b = buf.cpu()
-            assert bool((b[:256] == self.SENT).all()) and bool((b[256 + n:] == self.SENT).all()), f'{what}: a sentinel next to the output was overwritten'
-            if b.dtype.is_floating_point and what not in nan_ok:
-                assert not bool(torch.isnan(b[256:256 + n]).any()), f'{what}: {int(torch.isnan(b[256:256 + n]).sum())} elements were never written'
 
 
 def _sl(r, key, K):
