@@ -633,6 +633,24 @@ int tcct_gate_fusion_bwd(const void* dy, const float* field, void* dx1, void* dx
  * (the boundary-coordinate extractor the reference lacks -- it only carries the unused soft_argmax, nets/reg.py:27-35) */
 int tcct_mask_boundaries(const uint8_t* mask, int32_t* out, int N, int H, int W, int C, tcct_stream_t stream);
 
+/* ---- batched evaluation (eval.hip; KiteSeg.evaluate, tcct_amd/evalm.py): integer counts, bitwise reproducible ----
+ * pred: pred_kind 0 = fp32 logits NHWC [B,H,W,C], 1 = bf16 logits (same layout), 2 = uint8 class indices [B,H,W]; labels uint8 [B,H,W].  The class of a logit
+ * pixel is tcct_softmax_pick's: the first maximum under a strict `>` from -inf (a NaN never wins, all-NaN / all -inf -> class 0).  argmax uint8 [B,H,W]
+ * (nullable) is written for EVERY pixel; everything else counts the pixels y < h_valid, x < w_valid only (the image before the loader padded it):
+ *   counts   int32 [B,C,3]    {|pred&lab|, |pred|, |lab|} per image and class
+ *   bnd_pred int32 [B,C-1,W]  #{y < h_valid : class(y,x) < k}, k = 1..C-1 (tcct_mask_boundaries' counting definition); 0 in the columns x >= w_valid
+ *   bnd_lab  the same of the labels (bnd_pred and bnd_lab: both or neither)
+ * A class value >= C (label or uint8 prediction) adds to no count.  The call zeroes its outputs (one fill when counts, bnd_pred, bnd_lab lie back to back).
+ * C in 2..16, H*W < 2^31, B <= 65535. */
+int tcct_eval_counts(const void* pred, int pred_kind, const uint8_t* labels, int B, int H, int W, int C, int h_valid, int w_valid, int32_t* counts, int32_t* bnd_pred,
+                     int32_t* bnd_lab, uint8_t* argmax, tcct_stream_t stream);
+/* table fp64 [B, 4C-1], one row per image (the caller may point into a larger table): [0,C) Dice_c = (2I+1)/(P+G+1); [C,2C) IoU_c = (I+1)/(P+G-I+1) (the
+ * reference's MDiceLoss.score / MIouLoss.score with smooth = 1, in fp64 from the integers); [2C,3C-1) sum_x |bnd_pred - bnd_lab| per boundary; [3C-1,4C-2)
+ * sum_x (bnd_pred - bnd_lab)^2; [4C-2] n_col.  Sums run over the annotated columns (x < w_valid and bnd_lab[b][0][x] < h_valid: the label column holds a
+ * pixel of a class >= 1), reduced in int64 and then converted; n_col is their number.  bnd_pred == bnd_lab == NULL: those columns read 0. */
+int tcct_eval_scores(const int32_t* counts, const int32_t* bnd_pred, const int32_t* bnd_lab, int B, int C, int W, int h_valid, int w_valid, double* table,
+                     tcct_stream_t stream);
+
 /* ---- boundary-regression loss pieces (RegNet.regular_reg, nets/reg.py:109-156); this pipeline is fp32 -------- */
 int tcct_slice_channels_fwd(const void* x, float* y, int64_t M, int C, int start, int n, int dtype, tcct_stream_t stream);
 int tcct_slice_channels_bwd(const float* dy, void* dx, int64_t M, int C, int start, int n, int dtype, tcct_stream_t stream);

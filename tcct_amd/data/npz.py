@@ -92,6 +92,26 @@ class NpzEvalBatches:
             yield {'img': img, 'lab': lab, 'tag': [f'{self.ds.__name__}_{i}']}
 
 
+class NpzWholeBatches:
+    """whole images of one split in stored order, `bs` at a time (a ragged last batch is kept), no flips: what KiteSeg.evaluate scores"""
+
+    def __init__(self, ds, split, bs):
+        if bs < 1:
+            raise TcctError(f'evalSet: bs={bs}')
+        self.ds, self.split, self.bs = ds, split, int(bs)
+        self.n_images = split.N
+
+    def __len__(self):
+        return (self.split.N + self.bs - 1) // self.bs
+
+    def __iter__(self):
+        sp = self.split
+        for i in range(0, sp.N, self.bs):
+            img, lab = sp.img[i:i + self.bs], sp.lab[i:i + self.bs]
+            img = (img.permute(0, 3, 1, 2) if sp.C == 3 else img.unsqueeze(1)).float().div_(255).contiguous()
+            yield {'img': img, 'lab': lab, 'tag': [f'{self.ds.__name__}_{j}' for j in range(i, min(i + self.bs, sp.N))]}
+
+
 class NpzOCT:
     def __init__(self, path, crop=(256, 256), device=None, dbname=None):
         self.device = torch.device(device if device is not None else ('cuda' if torch.cuda.is_available() else 'cpu'))
@@ -149,6 +169,14 @@ class NpzOCT:
         if self.test is None:
             raise TcctError('this dataset file has no test_img / test_lab')
         return NpzEvalBatches(self, self.test, flips=False)
+
+    def evalSet(self, split='val', bs=8):
+        """whole images of 'train' | 'val' | 'test' in stored order, in batches of `bs`: img fp32 [b,C,H,W] = stored / 255, lab uint8 [b,H,W]"""
+        if split == 'test' and self.test is None:
+            raise TcctError('this dataset file has no test_img / test_lab')
+        if split not in ('train', 'val', 'test'):
+            raise TcctError(f"evalSet(split={split!r}): 'train', 'val' or 'test'")
+        return NpzWholeBatches(self, getattr(self, split), bs)
 
     def parse(self, pics):
         """-> (img fp32 [B,C,Hp,Wp], lab uint8 [B,Hp,Wp], tag, None) with Hp, Wp rounded up to multiples of 16 (zeros / class 0)"""

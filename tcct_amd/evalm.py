@@ -1,0 +1,144 @@
+"""Batched on-device evaluation: per-class Dice / IoU and layer-boundary position error of a whole split, without a host sync until the end.
+
+Two kernels (tcct_amd/csrc/eval.hip): `tcct_eval_counts` reads the logits once and leaves, per image, the integer class counts {I, P, G}, the boundary rows of
+prediction and label (the counting definition of `MaskOneHot.boundaries`) and, on request, the argmax mask; `tcct_eval_scores` turns them into one fp64 table
+row per image.  All accumulated quantities are integers, so every number is reproducible bit for bit.  Definitions ("Evaluation"):
+
+    Dice_c = (2 I + 1) / (P + G + 1)        IoU_c = (I + 1) / (P + G - I + 1)         (reference kite/losses/miou.py score(), smooth = 1)
+    boundary k of a column = number of its pixels of a class < k;  MAD / RMSE in pixels, pooled over the annotated columns of all images
+
+Only the pixels of the valid region (the image before the loader padded it to multiples of 16) are scored.  `aggregate` and `write_mask_png` are host functions."""
+import numpy as np
+import torch
+
+from ._lib import lib, TcctError
+
+_KIND = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2}
+
+
+def table_width(n_class):
+    return 4 * n_class - 1
+
+
+def _check(pred, lab, n_class, valid):
+    if not (torch.is_tensor(pred) and torch.is_tensor(lab) and pred.is_cuda and lab.is_cuda):
+        raise TcctError('eval_counts: prediction and labels must be CUDA tensors (no CPU fallback)')
+    if pred.dtype not in _KIND:
+        raise TcctError(f'eval_counts: prediction must be fp32 / bf16 logits [B,H,W,C] or uint8 classes [B,H,W], got {pred.dtype}')
+    kind = _KIND[pred.dtype]
+    if lab.dtype != torch.uint8 or lab.dim() != 3:
+        raise TcctError(f'eval_counts: labels must be uint8 class indices [B,H,W], got {lab.dtype}{tuple(lab.shape)}')
+    B, H, W = lab.shape
+    want = (B, H, W) if kind == 2 else (B, H, W, n_class)
+    if tuple(pred.shape) != want:
+        raise TcctError(f'eval_counts: prediction {tuple(pred.shape)} does not match labels {tuple(lab.shape)} with {n_class} classes (expected {want})')
+    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    return kind, B, H, W, hv, wv
+
+
+def eval_counts(pred, lab, n_class, valid=None, want_mask=False, want_boundaries=True):
+    """pred: fp32 / bf16 logits NHWC [B,H,W,C] or uint8 classes [B,H,W]; lab uint8 [B,H,W]; valid = (h_valid, w_valid), default the whole image.
+    -> (counts int32 [B,C,3], bnd_pred int32 [B,C-1,W] | None, bnd_lab | None, mask uint8 [B,H,W] | None).  One fill + one kernel, no sync."""
+    kind, B, H, W, hv, wv = _check(pred, lab, n_class, valid)
+    C = n_class
+    nc, nb = B * C * 3, B * (C - 1) * W
+    ws = torch.empty(nc + (2 * nb if want_boundaries else 0), device=lab.device, dtype=torch.int32)       # back to back: the call zeroes them with one fill
+    counts = ws[:nc].view(B, C, 3)
+    bp = ws[nc:nc + nb].view(B, C - 1, W) if want_boundaries else None
+    bl = ws[nc + nb:].view(B, C - 1, W) if want_boundaries else None
+    mask = torch.empty((B, H, W), device=lab.device, dtype=torch.uint8) if want_mask else None
+    lib.eval_counts(pred.contiguous(), kind, lab.contiguous(), B, H, W, C, hv, wv, counts, bp, bl, mask)
+    return counts, bp, bl, mask
+
+
+def eval_scores(counts, bnd_pred, bnd_lab, valid, table=None, row=0):
+    """counts / bnd_* as eval_counts returns them, valid = (h_valid, w_valid) -> fp64 [B, 4C-1] (module docstring of eval.hip / include/tcct_hip.h for the
+    columns).  With `table` (fp64 [N, 4C-1], contiguous) the rows go to table[row : row + B] and that slice is returned."""
+    B, C = counts.shape[0], counts.shape[1]
+    if bnd_pred is not None:
+        W = bnd_pred.shape[2]
+    else:
+        W = int(valid[1])
+    if table is None:
+        table, row = torch.empty((B, table_width(C)), device=counts.device, dtype=torch.float64), 0
+    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == table_width(C) and table.is_contiguous()):
+        raise TcctError(f'eval_scores: table must be a contiguous CUDA fp64 [N, {table_width(C)}]')
+    if row < 0 or row + B > table.shape[0]:
+        raise TcctError(f'eval_scores: rows {row}..{row + B} do not fit a table of {table.shape[0]} images')
+    out = table[row:row + B]
+    lib.eval_scores(counts, bnd_pred, bnd_lab, B, C, W, int(valid[0]), int(valid[1]), out)
+    return out
+
+
+def aggregate(table, n_class):
+    """per-image table (CPU tensor or numpy, [N, 4C-1]) -> dict: `dice`, `iou` [C] (means over images), `val_f1s` / `val_iou` (their means over classes 1..C-1,
+    what KiteSeg.val() reports), `mad`, `rmse` [C-1] in pixels pooled over the annotated columns of all images (NaN when there is none), `mad_mean`,
+    `n_images`, `n_columns`, `table`"""
+    C = n_class
+    t = np.asarray(table.detach().cpu().numpy() if torch.is_tensor(table) else table, dtype=np.float64).reshape(-1, table_width(C))
+    n = t.shape[0]
+    nan = np.full(C, np.nan)
+    dice = t[:, :C].mean(0) if n else nan.copy()
+    iou = t[:, C:2 * C].mean(0) if n else nan.copy()
+    ncol = float(t[:, 4 * C - 2].sum())
+    sabs, ssq = t[:, 2 * C:3 * C - 1].sum(0), t[:, 3 * C - 1:4 * C - 2].sum(0)
+    if ncol > 0:
+        mad, rmse = sabs / ncol, np.sqrt(ssq / ncol)
+    else:
+        mad, rmse = np.full(C - 1, np.nan), np.full(C - 1, np.nan)
+    return {'dice': dice, 'iou': iou, 'val_f1s': float(dice[1:].mean()), 'val_iou': float(iou[1:].mean()), 'mad': mad, 'rmse': rmse,
+            'mad_mean': float(mad.mean()), 'n_images': int(n), 'n_columns': int(ncol), 'table': t}
+
+
+def write_mask_png(path, mask_u8, divide=30):
+    """class-index mask [H,W] -> 8-bit gray PNG with gray = class * divide (the reference stores labels so, data/octnpy.py:96,123)"""
+    from PIL import Image
+    m = np.asarray(mask_u8.detach().cpu().numpy() if torch.is_tensor(mask_u8) else mask_u8)
+    if m.ndim != 2:
+        raise TcctError(f'write_mask_png: one [H,W] mask expected, got {m.shape}')
+    g = m.astype(np.int64) * int(divide)
+    if g.size and (g.min() < 0 or g.max() > 255):
+        raise TcctError(f'write_mask_png: class {int(m.max())} x {divide} does not fit 8 bits')
+    Image.fromarray(np.ascontiguousarray(g.astype(np.uint8))).save(path)      # a 2-D uint8 array is mode 'L'
+
+
+def read_mask_png(path, divide=30):
+    """inverse of write_mask_png -> uint8 [H,W] class indices"""
+    from PIL import Image
+    return (np.asarray(Image.open(path).convert('L')) // int(divide)).astype(np.uint8)
+
+
+def metrics_dict(res):
+    """the dict of `aggregate` without the table, as plain Python numbers (what metrics.json holds)"""
+    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res.items() if k != 'table'}
+
+
+def per_image_header(n_class):
+    C = n_class
+    return ([f'dice_{c}' for c in range(C)] + [f'iou_{c}' for c in range(C)] + [f'sum_abs_{k}' for k in range(1, C)] + [f'sum_sq_{k}' for k in range(1, C)]
+            + ['n_col'])
+
+
+class Evaluator:
+    """Scores of up to `n_images` images in a preallocated device table.  `add` launches the two kernels (and the fill of their workspace) and never syncs;
+    `result` makes ONE device -> host copy and aggregates on the host."""
+
+    def __init__(self, n_images, n_class, device):
+        if n_images < 1 or not 2 <= n_class <= 16:
+            raise TcctError(f'Evaluator: n_images={n_images}, n_class={n_class} (2..16)')
+        self.n_class, self.capacity, self.n = n_class, int(n_images), 0
+        self.table = torch.zeros((self.capacity, table_width(n_class)), device=device, dtype=torch.float64)
+
+    def add(self, pred, lab, valid=None, want_mask=False):
+        """one batch; -> the argmax mask uint8 [B,H,W] (device) when `want_mask`, else None"""
+        B, H, W = lab.shape
+        if self.n + B > self.capacity:
+            raise TcctError(f'Evaluator: {self.n} + {B} images exceed the {self.capacity} it was made for')
+        valid = (H, W) if valid is None else valid
+        counts, bp, bl, mask = eval_counts(pred, lab, self.n_class, valid, want_mask=want_mask)
+        eval_scores(counts, bp, bl, valid, table=self.table, row=self.n)
+        self.n += B
+        return mask
+
+    def result(self):
+        return aggregate(self.table[:self.n].cpu(), self.n_class)

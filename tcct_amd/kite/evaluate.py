@@ -1,0 +1,89 @@
+"""Score a checkpoint on a split: per-class Dice and IoU, per-boundary mean absolute distance and RMSE in pixels (KiteSeg.evaluate, tcct_amd/evalm.py).
+
+    python -m tcct_amd.kite.evaluate --db=npz:duke.npz --net=stc_tt --ckpt=exp_tcct-bp/val_top.pt --split=test --val_bs=8 --out=eval_out
+
+Takes the flags of kite/main.py that build the dataset and the network (--db --net --dtype --att --legacy_heads --crop), plus
+  --ckpt FILE   a state_dict `.pt` or a checkpoint `.npz`, loaded with checkpoint.load_reference_checkpoint: a layout or class-count mismatch raises
+                instead of scoring randomly initialised heads (default: ROOT/val_top.pt, what fit() writes)
+  --split       val | test | train          --val_bs  images per batch          --out DIR  masks as PNG (gray = class x 30), metrics.json, per_image.csv"""
+import argparse
+import os
+
+import torch
+
+from .main import str2bool, int_pair, parse_args as train_args
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description='KiteOCT evaluation')
+    p.add_argument('--db', type=str, default='synth', help='dataset')
+    p.add_argument('--net', type=str, default='stc_tt', help='network')
+    p.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'fp32'], help='compute dtype of activations')
+    p.add_argument('--att', type=str, default='pool', choices=['pool', 'factor', 'hydra'], help='token mixer of the ViT blocks (--net=stc_tt / tcct only)')
+    p.add_argument('--legacy_heads', type=str2bool, default=False, help="older head layout of the reference's shipped GOALS / HCMS / HEG checkpoints")
+    p.add_argument('--crop', type=int_pair, default=(256, 256), help='H,W of the training crops of --db=npz:FILE (evaluation reads whole images)')
+    p.add_argument('--gpu', type=str, default='0', help='cuda number')
+    p.add_argument('--root', type=str, default='', help='experiment folder (default exp_tcct-bp, as training)')
+    p.add_argument('--ckpt', type=str, default='', help='state_dict .pt or checkpoint .npz (default ROOT/val_top.pt)')
+    p.add_argument('--split', type=str, default='val', choices=['val', 'test', 'train'])
+    p.add_argument('--val_bs', type=int, default=8, help='images per evaluation batch')
+    p.add_argument('--out', type=str, default='', help='folder for the predicted masks, metrics.json and per_image.csv')
+    p.add_argument('--bug', type=str2bool, default=False, help='Debug Mode: ten batches')
+    return p
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.legacy_heads and args.net not in ('stc_tt', 'tcct'):
+        raise SystemExit('--legacy_heads=true is only offered for --net=stc_tt')
+    if args.att != 'pool' and args.net not in ('stc_tt', 'tcct'):
+        raise SystemExit(f'--att={args.att} is only offered for --net=stc_tt')
+    if args.val_bs < 1:
+        raise SystemExit(f'--val_bs={args.val_bs}')
+    return args
+
+
+def report(res):
+    """the printed summary of an `evalm.aggregate` dict"""
+    C = len(res['dice'])
+    lines = [f"{res['n_images']} images, {res['n_columns']} annotated columns",
+             'class    ' + ' '.join(f'{c:>7d}' for c in range(C)) + '   mean(1..)',
+             'Dice     ' + ' '.join(f'{v:7.4f}' for v in res['dice']) + f"   {res['val_f1s']:.4f}",
+             'IoU      ' + ' '.join(f'{v:7.4f}' for v in res['iou']) + f"   {res['val_iou']:.4f}",
+             'boundary ' + ' '.join(f'{k:>7d}' for k in range(1, C)) + '   mean',
+             'MAD px   ' + ' '.join(f'{v:7.3f}' for v in res['mad']) + f"   {res['mad_mean']:.3f}",
+             'RMSE px  ' + ' '.join(f'{v:7.3f}' for v in res['rmse'])]
+    return '\n'.join(lines)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from .. import nets
+    from ..checkpoint import load_reference_checkpoint
+    from ..data import EyeSetGenerator
+    from .loop_seg import KiteSeg
+    dataset = EyeSetGenerator(dbname=args.db, **(dict(crop=args.crop) if args.db.startswith('npz:') else {}))
+    factory = getattr(nets, args.net, None)
+    if factory is None:
+        raise SystemExit(f'--net={args.net}: unknown network')
+    kw = dict(compute_dtype=torch.bfloat16 if args.dtype == 'bf16' else torch.float32)
+    if args.att != 'pool':
+        kw['att'] = args.att
+    if args.legacy_heads:
+        kw['legacy_heads'] = True
+    net = nets.RegNet(factory(dataset.out_channels, **kw), out_channels=dataset.out_channels)
+    # KiteSeg reads the training flags too (criterion, optimizer): they take main.py's defaults
+    kargs = train_args([])
+    for k in ('db', 'net', 'dtype', 'att', 'legacy_heads', 'crop', 'gpu', 'root', 'bug'):
+        setattr(kargs, k, getattr(args, k))
+    keras = KiteSeg(model=net, dataset=dataset, root=args.root, args=kargs)
+    ckpt = args.ckpt or os.path.join(keras.root, 'val_top.pt')
+    missing, unexpected = load_reference_checkpoint(keras.model, ckpt)
+    print(f'loaded model: {ckpt} ({len(missing)} missing, {len(unexpected)} unexpected keys)')
+    res = keras.evaluate(split=args.split, bs=args.val_bs, out_dir=args.out or None)
+    print(report(res))
+    return res
+
+
+if __name__ == '__main__':
+    main()

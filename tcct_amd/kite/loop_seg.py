@@ -131,6 +131,58 @@ class KiteSeg(KiteBack):
         print('*SCORES:*', sc, '->', sc[1:].mean())
         return logs
 
+    def _eval_batches(self, split, bs):
+        ds = self.dataset
+        if hasattr(ds, 'evalSet'):
+            return ds.evalSet(split, bs)
+        if split == 'val':
+            return ds.valSet(bs=bs)
+        if split == 'test':
+            return ds.testSet(bs=bs)
+        raise TcctError(f"evaluate(split={split!r}): this dataset has no evalSet(); only 'val' and 'test' are available")
+
+    def evaluate(self, split='val', bs=8, out_dir=None, flagDebug=False):
+        """Scores of a whole split in batches (tcct_amd/evalm.py): per-class Dice / IoU and per-boundary MAD / RMSE of the valid region (the image before
+        `parse` padded it).  Eval mode, no gradients, main head only; the logits go straight to the counting kernel and nothing is read back before the end
+        -- unless `out_dir` is given: then the mask of every batch is copied to the host and written as `{split}_{index:05d}.png` (gray = class x 30, cropped
+        to the valid region), next to `metrics.json` and `per_image.csv`.  Returns the dict of `evalm.aggregate` (`val_f1s` / `val_iou` as `val()` defines them)."""
+        import os
+        from .. import evalm
+        from ..nets.reg import as_label_index
+        batches = self._eval_batches(split, bs)
+        n_max = int(getattr(batches, 'n_images', len(batches) * bs))
+        ev = evalm.Evaluator(max(n_max, 1), self.NB_CLASS, self.device)
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+        prev = torch.is_grad_enabled()
+        torch.set_grad_enabled(False)
+        self.model.eval()
+        try:
+            for i, imgs in enumerate(batches):
+                valid = tuple(int(v) for v in imgs['img'].shape[-2:])       # before parse() pads H and W to multiples of 16
+                img, lab, _, _ = self.dataset.parse(imgs)
+                lab = as_label_index(self.cuda(lab))
+                lg = as_nhwc(self.predict(img, softmax=False))
+                first = ev.n
+                mask = ev.add(lg, lab, valid, want_mask=out_dir is not None)
+                if out_dir is not None:
+                    m = mask[:, :valid[0], :valid[1]].cpu().numpy()
+                    for j in range(m.shape[0]):
+                        evalm.write_mask_png(os.path.join(out_dir, f'{split}_{first + j:05d}.png'), m[j])
+                if (self.args.bug or flagDebug) and i > 8:
+                    break
+        finally:
+            torch.set_grad_enabled(prev)
+        res = ev.result()                       # the ONE device -> host copy
+        print('*SCORES:*', np.round(res['dice'], 4), '->', round(res['val_f1s'], 4))
+        if out_dir is not None:
+            import json
+            with open(os.path.join(out_dir, 'metrics.json'), 'w') as f:
+                json.dump(evalm.metrics_dict(res), f, indent=1)
+            np.savetxt(os.path.join(out_dir, 'per_image.csv'), res['table'], delimiter=',', header=','.join(evalm.per_image_header(self.NB_CLASS)), comments='',
+                       fmt='%.17g')
+        return res
+
     def train_step(self, img, lab):
         """one optimisation step (reference loop_seg.py:121-130); returns the loss TENSOR (no host sync)"""
         from .. import ops
