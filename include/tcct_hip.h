@@ -650,6 +650,18 @@ int tcct_eval_counts(const void* pred, int pred_kind, const uint8_t* labels, int
  * pixel of a class >= 1), reduced in int64 and then converted; n_col is their number.  bnd_pred == bnd_lab == NULL: those columns read 0. */
 int tcct_eval_scores(const int32_t* counts, const int32_t* bnd_pred, const int32_t* bnd_lab, int B, int C, int W, int h_valid, int w_valid, double* table,
                      tcct_stream_t stream);
+/* Ordered layer decode (decode.hip; evalm.ordered_decode): per image and valid column the class sequence c(0) <= c(1) <= ... <= c(h_valid-1) that
+ * maximises sum_y q(y, c(y)), q = (int32) rint(clamp(s, -1024, 1024) * 256) of the logit s (NaN -> the lower clamp; rint = round half to even), by a dynamic
+ * programme down the column.  Of all maximisers the result is the lexicographically smallest when the rows are read from h_valid-1 up to 0.  Classes are
+ * assumed to increase with depth, as in the evaluation above (no class-order permutation, no "background above and below" wrap).
+ * logits: kind 0 = fp32 NHWC [B,H,W,C], 1 = bf16 (tcct_eval_counts' pred_kind codes).  take_ws: workspace of B*H*W words of 1 byte (C <= 8) or 2 bytes.
+ *   mask    uint8 [B,H,W]     the ordered class for y < h_valid, x < w_valid, 0 elsewhere (every pixel is written)
+ *   bnd     int32 [B,C-1,W]   #{y < h_valid : c(y) < k}, k = 1..C-1 (tcct_mask_boundaries' counting definition), non-decreasing in k; 0 for x >= w_valid
+ *   changed int32 [B]         valid pixels whose ordered class differs from the first argmax of q at that pixel (zeroed by the call, then accumulated)
+ *   best    int32 [B,W]       (nullable) the optimal total of each valid column, 0 elsewhere
+ * C in 2..16, h_valid <= min(H, 4096) (|sum| <= 4096 * 2^18 = 2^30 fits int32), w_valid <= W, B <= 65535; h_valid == 0 or w_valid == 0 zeroes every output. */
+int tcct_ordered_decode(const void* logits, int kind, int B, int H, int W, int C, int h_valid, int w_valid, void* take_ws, uint8_t* mask, int32_t* bnd,
+                        int32_t* changed, int32_t* best, tcct_stream_t stream);
 
 /* ---- boundary-regression loss pieces (RegNet.regular_reg, nets/reg.py:109-156); this pipeline is fp32 -------- */
 int tcct_slice_channels_fwd(const void* x, float* y, int64_t M, int C, int start, int n, int dtype, tcct_stream_t stream);

@@ -7,13 +7,25 @@ row per image.  All accumulated quantities are integers, so every number is repr
     Dice_c = (2 I + 1) / (P + G + 1)        IoU_c = (I + 1) / (P + G - I + 1)         (reference kite/losses/miou.py score(), smooth = 1)
     boundary k of a column = number of its pixels of a class < k;  MAD / RMSE in pixels, pooled over the annotated columns of all images
 
-Only the pixels of the valid region (the image before the loader padded it to multiples of 16) are scored.  `aggregate` and `write_mask_png` are host functions."""
+Only the pixels of the valid region (the image before the loader padded it to multiples of 16) are scored.  `aggregate` and `write_mask_png` are host functions.
+
+`ordered_decode` (tcct_amd/csrc/decode.hip) replaces the per-pixel argmax by the best class sequence that never decreases down a column: a mask whose
+boundary rows are layer positions by construction.  `Evaluator.add(..., decode='ordered')` scores that mask through the same two kernels."""
 import numpy as np
 import torch
 
 from ._lib import lib, TcctError
 
 _KIND = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2}
+
+
+DECODES = ('argmax', 'ordered')
+
+
+def check_decode(decode):
+    if decode not in DECODES:
+        raise TcctError(f"decode={decode!r}: 'argmax' (the per-pixel maximum) or 'ordered' (classes non-decreasing down every column)")
+    return decode
 
 
 def table_width(n_class):
@@ -49,6 +61,31 @@ def eval_counts(pred, lab, n_class, valid=None, want_mask=False, want_boundaries
     mask = torch.empty((B, H, W), device=lab.device, dtype=torch.uint8) if want_mask else None
     lib.eval_counts(pred.contiguous(), kind, lab.contiguous(), B, H, W, C, hv, wv, counts, bp, bl, mask)
     return counts, bp, bl, mask
+
+
+def ordered_decode(logits, n_class, valid=None, want_best=False):
+    """Ordered layer decode (decode.hip): per image and valid column the non-decreasing class sequence down the rows that maximises the summed integer
+    scores q = rint(clamp(logit, -1024, 1024) * 256); of all maximisers the lexicographically smallest when the rows are read from the last valid row up.
+    Classes are assumed to increase with depth, as everywhere in this module: no class-order permutation, no "background above and below" wrap.
+    logits: fp32 / bf16 NHWC [B,H,W,C]; valid = (h_valid, w_valid), default the whole image, h_valid <= 4096.
+    -> (mask uint8 [B,H,W], 0 outside the valid region; bnd int32 [B,C-1,W], the boundary rows of the mask (non-decreasing in k); changed int32 [B], the valid
+    pixels whose class differs from the first argmax of q; best int32 [B,W] | None, the optimal total of each column).  Allocates its workspace, no sync."""
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        raise TcctError('ordered_decode: logits must be a CUDA tensor (no CPU fallback)')
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TcctError(f'ordered_decode: logits must be fp32 / bf16 [B,H,W,C], got {logits.dtype}')
+    if logits.dim() != 4 or logits.shape[3] != n_class:
+        raise TcctError(f'ordered_decode: logits {tuple(logits.shape)} are not NHWC [B,H,W,{n_class}]')
+    B, H, W, C = logits.shape
+    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    dev = logits.device
+    take = torch.empty((B, H, W), device=dev, dtype=torch.uint8 if C <= 8 else torch.int16)
+    mask = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+    bnd = torch.empty((B, max(C - 1, 0), W), device=dev, dtype=torch.int32)
+    changed = torch.empty((B,), device=dev, dtype=torch.int32)
+    best = torch.empty((B, W), device=dev, dtype=torch.int32) if want_best else None
+    lib.ordered_decode(logits.contiguous(), _KIND[logits.dtype], B, H, W, C, hv, wv, take, mask, bnd, changed, best)
+    return mask, bnd, changed, best
 
 
 def eval_scores(counts, bnd_pred, bnd_lab, valid, table=None, row=0):
@@ -128,17 +165,38 @@ class Evaluator:
             raise TcctError(f'Evaluator: n_images={n_images}, n_class={n_class} (2..16)')
         self.n_class, self.capacity, self.n = n_class, int(n_images), 0
         self.table = torch.zeros((self.capacity, table_width(n_class)), device=device, dtype=torch.float64)
+        self.decode, self.changed = 'argmax', None
 
-    def add(self, pred, lab, valid=None, want_mask=False):
-        """one batch; -> the argmax mask uint8 [B,H,W] (device) when `want_mask`, else None"""
+    def add(self, pred, lab, valid=None, want_mask=False, decode='argmax'):
+        """one batch; -> the scored mask uint8 [B,H,W] (device) when `want_mask`, else None.  decode='argmax': the per-pixel first maximum of the logits;
+        'ordered': the logits go through `ordered_decode` first and its mask is what is scored (and returned); all batches of one Evaluator decode alike"""
+        check_decode(decode)
         B, H, W = lab.shape
         if self.n + B > self.capacity:
             raise TcctError(f'Evaluator: {self.n} + {B} images exceed the {self.capacity} it was made for')
+        if self.n and decode != self.decode:
+            raise TcctError(f"Evaluator: decode={decode!r} after batches with decode={self.decode!r}")
+        self.decode = decode
         valid = (H, W) if valid is None else valid
-        counts, bp, bl, mask = eval_counts(pred, lab, self.n_class, valid, want_mask=want_mask)
+        if decode == 'ordered':
+            _check(pred, lab, self.n_class, valid)
+            if pred.dtype == torch.uint8:
+                raise TcctError("Evaluator: decode='ordered' needs logits, not a uint8 class mask")
+            omask, _, changed, _ = ordered_decode(pred, self.n_class, valid)
+            if self.changed is None:
+                self.changed = torch.zeros((), device=changed.device, dtype=torch.int64)
+            self.changed += changed.sum()                   # stays on the device
+            counts, bp, bl, _ = eval_counts(omask, lab, self.n_class, valid)
+            mask = omask if want_mask else None
+        else:
+            counts, bp, bl, mask = eval_counts(pred, lab, self.n_class, valid, want_mask=want_mask)
         eval_scores(counts, bp, bl, valid, table=self.table, row=self.n)
         self.n += B
         return mask
 
     def result(self):
-        return aggregate(self.table[:self.n].cpu(), self.n_class)
+        res = aggregate(self.table[:self.n].cpu(), self.n_class)
+        if self.decode == 'ordered':
+            res['decode'] = 'ordered'
+            res['changed_pixels'] = int(self.changed.item()) if self.changed is not None else 0
+        return res

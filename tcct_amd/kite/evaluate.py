@@ -5,7 +5,8 @@
 Takes the flags of kite/main.py that build the dataset and the network (--db --net --dtype --att --legacy_heads --crop), plus
   --ckpt FILE   a state_dict `.pt` or a checkpoint `.npz`, loaded with checkpoint.load_reference_checkpoint: a layout or class-count mismatch raises
                 instead of scoring randomly initialised heads (default: ROOT/val_top.pt, what fit() writes)
-  --split       val | test | train          --val_bs  images per batch          --out DIR  masks as PNG (gray = class x 30), metrics.json, per_image.csv"""
+  --split       val | test | train          --val_bs  images per batch          --out DIR  masks as PNG (gray = class x 30), metrics.json, per_image.csv
+  --decode      argmax (default) | ordered: score and write the masks of evalm.ordered_decode, classes non-decreasing down every column"""
 import argparse
 import os
 
@@ -28,6 +29,7 @@ def build_parser():
     p.add_argument('--split', type=str, default='val', choices=['val', 'test', 'train'])
     p.add_argument('--val_bs', type=int, default=8, help='images per evaluation batch')
     p.add_argument('--out', type=str, default='', help='folder for the predicted masks, metrics.json and per_image.csv')
+    p.add_argument('--decode', type=str, default='argmax', choices=['argmax', 'ordered'], help='per-pixel argmax, or the ordered layer decode (DESIGN 6c)')
     p.add_argument('--bug', type=str2bool, default=False, help='Debug Mode: ten batches')
     return p
 
@@ -53,6 +55,8 @@ def report(res):
              'boundary ' + ' '.join(f'{k:>7d}' for k in range(1, C)) + '   mean',
              'MAD px   ' + ' '.join(f'{v:7.3f}' for v in res['mad']) + f"   {res['mad_mean']:.3f}",
              'RMSE px  ' + ' '.join(f'{v:7.3f}' for v in res['rmse'])]
+    if 'decode' in res:
+        lines.append(f"decode   {res['decode']}: {res['changed_pixels']} pixels differ from the per-pixel argmax")
     return '\n'.join(lines)
 
 
@@ -80,7 +84,7 @@ def main(argv=None):
     ckpt = args.ckpt or os.path.join(keras.root, 'val_top.pt')
     missing, unexpected = load_reference_checkpoint(keras.model, ckpt)
     print(f'loaded model: {ckpt} ({len(missing)} missing, {len(unexpected)} unexpected keys)')
-    res = keras.evaluate(split=args.split, bs=args.val_bs, out_dir=args.out or None)
+    res = keras.evaluate(split=args.split, bs=args.val_bs, out_dir=args.out or None, decode=args.decode)
     print(report(res))
     return res
 

@@ -50,12 +50,15 @@ class KiteSeg(KiteBack):
             base.eager_feats = udh and os.environ.get('TCCT_EAGER_FEATS', '1') != '0'
             base.compose_heads = not udh
 
-    def predict(self, img, softmax=True, *args):
+    def predict(self, img, softmax=True, *args, decode='argmax'):
         """reference loop_seg.py:21-33: one_hot(argmax(softmax(out[0]))).  Returns a lazy MaskOneHot (class-index map;
-        `.dense()` gives the reference's float [B,C,H,W]) when softmax=True, else the raw logits."""
+        `.dense()` gives the reference's float [B,C,H,W]) when softmax=True, else the raw logits.  decode='ordered' (with softmax=True): the mask is
+        `evalm.ordered_decode`'s, classes non-decreasing down every column, instead of the per-pixel argmax; the hipGraph replay is not used then."""
+        from ..evalm import check_decode
+        ordered = check_decode(decode) == 'ordered'
         with torch.no_grad():
             img = self.cuda(img)
-            if softmax and self.use_graph and not self.model.training and img.is_cuda and img.shape[0] <= 2:
+            if softmax and not ordered and self.use_graph and not self.model.training and img.is_cuda and img.shape[0] <= 2:
                 # launch-bound regime (validation runs bs=1): replay the captured kernel sequence (tcct_amd/graph.py)
                 if self._graphed is None:
                     from ..graph import GraphedPredict
@@ -77,8 +80,12 @@ class KiteSeg(KiteBack):
             if softmax:
                 lg = as_nhwc(pred)
                 B, H, W, C = lg.shape
-                idx = torch.empty((B, H, W), device=lg.device, dtype=torch.uint8)
-                lib.softmax_pick(lg, None, B * H * W, C, None, idx, 0 if lg.dtype == torch.float32 else 1)
+                if ordered:
+                    from ..evalm import ordered_decode
+                    idx = ordered_decode(lg, C)[0]
+                else:
+                    idx = torch.empty((B, H, W), device=lg.device, dtype=torch.uint8)
+                    lib.softmax_pick(lg, None, B * H * W, C, None, idx, 0 if lg.dtype == torch.float32 else 1)
                 pred = MaskOneHot(idx, self.NB_CLASS)
         return pred
 
@@ -141,13 +148,16 @@ class KiteSeg(KiteBack):
             return ds.testSet(bs=bs)
         raise TcctError(f"evaluate(split={split!r}): this dataset has no evalSet(); only 'val' and 'test' are available")
 
-    def evaluate(self, split='val', bs=8, out_dir=None, flagDebug=False):
+    def evaluate(self, split='val', bs=8, out_dir=None, flagDebug=False, decode='argmax'):
         """Scores of a whole split in batches (tcct_amd/evalm.py): per-class Dice / IoU and per-boundary MAD / RMSE of the valid region (the image before
         `parse` padded it).  Eval mode, no gradients, main head only; the logits go straight to the counting kernel and nothing is read back before the end
         -- unless `out_dir` is given: then the mask of every batch is copied to the host and written as `{split}_{index:05d}.png` (gray = class x 30, cropped
-        to the valid region), next to `metrics.json` and `per_image.csv`.  Returns the dict of `evalm.aggregate` (`val_f1s` / `val_iou` as `val()` defines them)."""
+        to the valid region), next to `metrics.json` and `per_image.csv`.  Returns the dict of `evalm.aggregate` (`val_f1s` / `val_iou` as `val()` defines them).
+        decode='ordered': the logits of every batch go through `evalm.ordered_decode` (classes non-decreasing down every column of the valid region) and that
+        mask is what is scored and written; the result and `metrics.json` then also carry `decode` and `changed_pixels` (pixels that differ from the argmax)."""
         import os
         from .. import evalm
+        evalm.check_decode(decode)
         from ..nets.reg import as_label_index
         batches = self._eval_batches(split, bs)
         n_max = int(getattr(batches, 'n_images', len(batches) * bs))
@@ -164,7 +174,7 @@ class KiteSeg(KiteBack):
                 lab = as_label_index(self.cuda(lab))
                 lg = as_nhwc(self.predict(img, softmax=False))
                 first = ev.n
-                mask = ev.add(lg, lab, valid, want_mask=out_dir is not None)
+                mask = ev.add(lg, lab, valid, want_mask=out_dir is not None, decode=decode)
                 if out_dir is not None:
                     m = mask[:, :valid[0], :valid[1]].cpu().numpy()
                     for j in range(m.shape[0]):
