@@ -653,7 +653,8 @@ int tcct_eval_scores(const int32_t* counts, const int32_t* bnd_pred, const int32
 /* Ordered layer decode (decode.hip; evalm.ordered_decode): per image and valid column the class sequence c(0) <= c(1) <= ... <= c(h_valid-1) that
  * maximises sum_y q(y, c(y)), q = (int32) rint(clamp(s, -1024, 1024) * 256) of the logit s (NaN -> the lower clamp; rint = round half to even), by a dynamic
  * programme down the column.  Of all maximisers the result is the lexicographically smallest when the rows are read from h_valid-1 up to 0.  Classes are
- * assumed to increase with depth, as in the evaluation above (no class-order permutation, no "background above and below" wrap).
+ * assumed to increase with depth, as in the evaluation above; a class order of its own, background above AND below the layers or lesion classes are what
+ * tcct_layout_decode below is for.
  * logits: kind 0 = fp32 NHWC [B,H,W,C], 1 = bf16 (tcct_eval_counts' pred_kind codes).  take_ws: workspace of B*H*W words of 1 byte (C <= 8) or 2 bytes.
  *   mask    uint8 [B,H,W]     the ordered class for y < h_valid, x < w_valid, 0 elsewhere (every pixel is written)
  *   bnd     int32 [B,C-1,W]   #{y < h_valid : c(y) < k}, k = 1..C-1 (tcct_mask_boundaries' counting definition), non-decreasing in k; 0 for x >= w_valid
@@ -662,6 +663,31 @@ int tcct_eval_scores(const int32_t* counts, const int32_t* bnd_pred, const int32
  * C in 2..16, h_valid <= min(H, 4096) (|sum| <= 4096 * 2^18 = 2^30 fits int32), w_valid <= W, B <= 65535; h_valid == 0 or w_valid == 0 zeroes every output. */
 int tcct_ordered_decode(const void* logits, int kind, int B, int H, int W, int C, int h_valid, int w_valid, void* take_ws, uint8_t* mask, int32_t* bnd,
                         int32_t* changed, int32_t* best, tcct_stream_t stream);
+/* Layout decode (layout_decode.hip; evalm.layout_decode): the ordered decode over a LAYOUT instead of over the classes.  layers[S] (host array) is
+ * the top-to-bottom sequence of states, each with a class in [0,C) (adjacent entries differ, repeats allowed: 0,1,..,C-1,0 is "background on both sides");
+ * free_mask has bit f set for every free class f (a lesion: any state may emit it).  Every class of [0,C) is in exactly one of the two; 2 <= S <= 16.
+ * pred: kind 0 = fp32 logits NHWC [B,H,W,C], 1 = bf16, q = tcct_ordered_decode's quantiser; kind 2 = uint8 classes [B,H,W] (labels or an argmax mask),
+ * q(y,c) = 256 where the pixel equals c, else 0 (a value >= C: 0 for every class).  With F(y) = the first maximum of q(y,f) over the free classes in ascending
+ * order and f*(y) its class, state s emits e(y,s) = max(q(y,layers[s]), F(y)) (= q(y,layers[s]) without free classes) and shows class layers[s] when
+ * q(y,layers[s]) >= F(y), else f*(y).  The state sequence s(0) <= s(1) <= ... <= s(h_valid-1) maximises sum_y e(y,s(y)); recurrence, backtrack and tie rule are
+ * tcct_ordered_decode's with e for q and states for classes.  With layers = 0..C-1 and no free class every output equals tcct_ordered_decode's.
+ * ws: workspace of tcct_layout_decode_ws_bytes(B,H,W,S,n_free) bytes (n_free = the number of bits of free_mask).
+ *   mask    uint8 [B,H,W]     the shown class for y < h_valid, x < w_valid, 0 elsewhere (every pixel is written)
+ *   bnd     int32 [B,S-1,W]   #{y < h_valid : s(y) < k}, k = 1..S-1: the row at which state k starts (through lesion pixels, past a repeated background),
+ *                             non-decreasing in k; 0 for x >= w_valid
+ *   changed int32 [B]         valid pixels whose shown class differs from the first argmax of q over all C classes (zeroed by the call, then accumulated)
+ *   best    int32 [B,W]       (nullable) the optimal total of each valid column, 0 elsewhere
+ *   state   uint8 [B,H,W]     (nullable) s(y) in the valid region, 0 elsewhere
+ * C in 2..16, h_valid <= min(H, 4096), w_valid <= W, B <= 65535, H*W*C*4 < 2^31; h_valid == 0 or w_valid == 0 zeroes every output without a launch. */
+int64_t tcct_layout_decode_ws_bytes(int B, int H, int W, int S, int n_free);
+int tcct_layout_decode(const void* pred, int kind, int B, int H, int W, int C, const int* layers, int S, int free_mask, int h_valid, int w_valid, void* ws,
+                       uint8_t* mask, int32_t* bnd, int32_t* changed, int32_t* best, uint8_t* state, tcct_stream_t stream);
+/* tcct_eval_scores under a layout: counts int32 [B,C,3] of the decoded mask against the label (tcct_eval_counts), bnd_pred / bnd_lab int32 [B,S-1,W] the
+ * surfaces of tcct_layout_decode of the prediction and of the label (kind 2).  table fp64 [B, 2C + 2(S-1) + 1]: [0,C) Dice_c; [C,2C) IoU_c; [2C, 2C+S-1)
+ * sum_x |bnd_pred - bnd_lab| per surface; [2C+S-1, 2C+2(S-1)) sum_x (bnd_pred - bnd_lab)^2; last n_col.  Annotated columns as tcct_eval_scores: x < w_valid
+ * and bnd_lab[b][0][x] < h_valid; int64 sums, converted once. */
+int tcct_eval_layout_scores(const int32_t* counts, const int32_t* bnd_pred, const int32_t* bnd_lab, int B, int C, int S, int W, int h_valid, int w_valid,
+                            double* table, tcct_stream_t stream);
 
 /* ---- boundary-regression loss pieces (RegNet.regular_reg, nets/reg.py:109-156); this pipeline is fp32 -------- */
 int tcct_slice_channels_fwd(const void* x, float* y, int64_t M, int C, int start, int n, int dtype, tcct_stream_t stream);

@@ -4,7 +4,8 @@ ALB_TWIST recipe (data/octgen.py:9-18) and ToTensor lines (data/octgen.py:124-12
 host sync per step: the draws come from a private device generator, seeded once per iterator from the global CPU generator.
 
 Arrays of the file: `train_img` uint8 [N,H,W] or [N,H,W,3], `train_lab` uint8 class indices [N,H,W], optional `val_img`/`val_lab` (default: the
-training images, as reference data/octnpy.py:40-41) and `test_img`/`test_lab`, `n_class`."""
+training images, as reference data/octnpy.py:40-41) and `test_img`/`test_lab`, `n_class`, optional `layers` / `free` (int class ids: the layout of
+`evalm.Layout`, exposed as `NpzOCT.layout`)."""
 import numpy as np
 import torch
 
@@ -130,6 +131,11 @@ class NpzOCT:
             self.train = _Split(z['train_img'], z['train_lab'], self.device, 'train')
             self.val = _Split(z['val_img'], z['val_lab'], self.device, 'val') if 'val_img' in z else self.train
             self.test = _Split(z['test_img'], z['test_lab'], self.device, 'test') if 'test_img' in z else None
+            # how the classes lie in a column (pack_dataset.py --layers / --free); None: classes increase with depth
+            self.layout = None
+            if 'layers' in z:
+                from ..evalm import Layout
+                self.layout = Layout(z['layers'].tolist(), z['free'].tolist() if 'free' in z else (), self.out_channels)
         self.passes = max(1, EPOCH_IMAGES // self.train.N)
         tr = self.train
         self.rowcount = torch.empty((tr.N, tr.H + 1), device=self.device, dtype=torch.int32)

@@ -10,7 +10,13 @@ row per image.  All accumulated quantities are integers, so every number is repr
 Only the pixels of the valid region (the image before the loader padded it to multiples of 16) are scored.  `aggregate` and `write_mask_png` are host functions.
 
 `ordered_decode` (tcct_amd/csrc/decode.hip) replaces the per-pixel argmax by the best class sequence that never decreases down a column: a mask whose
-boundary rows are layer positions by construction.  `Evaluator.add(..., decode='ordered')` scores that mask through the same two kernels."""
+boundary rows are layer positions by construction.  `Evaluator.add(..., decode='ordered')` scores that mask through the same two kernels.
+
+`Layout` / `layout_decode` (tcct_amd/csrc/layout_decode.hip) carry the same decode over a layout: a top-to-bottom sequence of states whose classes
+may repeat (background above and below the retina) plus free classes (lesions) that may sit anywhere.  `Evaluator(..., layout=...)` decodes prediction AND
+label through it and scores the surfaces between the states (`tcct_eval_layout_scores`)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -28,8 +34,62 @@ def check_decode(decode):
     return decode
 
 
-def table_width(n_class):
-    return 4 * n_class - 1
+class Layout:
+    """How the classes lie in a column.  `layers`: the classes of the S states from top to bottom, 2 <= S <= 16, adjacent entries differ, a class
+    may come back (0,1,..,C-1,0: background on both sides).  `free`: classes that are no layer (fluid, lesions) and may show inside any state.  Every class of
+    [0, n_class) is in exactly one of the two; n_class defaults to the largest class named + 1.  Anything else raises TcctError."""
+
+    def __init__(self, layers, free=(), n_class=None):
+        try:
+            layers, free = tuple(int(c) for c in layers), tuple(sorted(int(c) for c in free))
+        except (TypeError, ValueError):
+            raise TcctError(f'Layout: layers={layers!r}, free={free!r}: sequences of class ids expected')
+        C = int(n_class) if n_class is not None else max(layers + free, default=0) + 1
+        if not 2 <= C <= 16:
+            raise TcctError(f'Layout: n_class={C} (2..16)')
+        if not 2 <= len(layers) <= 16:
+            raise TcctError(f'Layout: {len(layers)} states (2..16)')
+        if any(not 0 <= c < C for c in layers + free):
+            raise TcctError(f'Layout: layers={layers}, free={free}: a class outside 0..{C - 1}')
+        if any(a == b for a, b in zip(layers, layers[1:])):
+            raise TcctError(f'Layout: layers={layers}: a state repeats the class of the state above it')
+        if len(set(free)) != len(free) or set(free) & set(layers):
+            raise TcctError(f'Layout: layers={layers}, free={free}: a class is named twice')
+        if set(free) | set(layers) != set(range(C)):
+            raise TcctError(f'Layout: layers={layers}, free={free}: class {min(set(range(C)) - set(free) - set(layers))} is neither a layer nor free')
+        self.layers, self.free, self.n_class, self.n_states = layers, free, C, len(layers)
+        self.free_mask = sum(1 << f for f in free)
+        self._c_layers = (ctypes.c_int * len(layers))(*layers)
+
+    @classmethod
+    def identity(cls, n_class):
+        """classes increase with depth, no free class: what `ordered_decode` assumes"""
+        return cls(tuple(range(int(n_class))), (), n_class)
+
+    def surface_names(self):
+        """surface k (1..S-1) lies between states k-1 and k: 'class above|class below'"""
+        return [f'{a}|{b}' for a, b in zip(self.layers, self.layers[1:])]
+
+    def __eq__(self, other):
+        return isinstance(other, Layout) and (self.layers, self.free, self.n_class) == (other.layers, other.free, other.n_class)
+
+    def __hash__(self):
+        return hash((self.layers, self.free, self.n_class))
+
+    def __repr__(self):
+        return f'Layout(layers={self.layers}, free={self.free}, n_class={self.n_class})'
+
+
+def check_layout_decode(layout, decode):
+    """a layout belongs to the ordered decode: together with the per-pixel argmax it raises"""
+    if layout is not None and not isinstance(layout, Layout):
+        raise TcctError(f'layout must be an evalm.Layout, got {type(layout).__name__}')
+    if layout is not None and decode != 'ordered':
+        raise TcctError(f"a layout describes the ordered decode; decode={decode!r} has no use for it (pass decode='ordered')")
+
+
+def table_width(n_class, layout=None):
+    return 4 * n_class - 1 if layout is None else 2 * n_class + 2 * (layout.n_states - 1) + 1
 
 
 def _check(pred, lab, n_class, valid):
@@ -66,7 +126,7 @@ def eval_counts(pred, lab, n_class, valid=None, want_mask=False, want_boundaries
 def ordered_decode(logits, n_class, valid=None, want_best=False):
     """Ordered layer decode (decode.hip): per image and valid column the non-decreasing class sequence down the rows that maximises the summed integer
     scores q = rint(clamp(logit, -1024, 1024) * 256); of all maximisers the lexicographically smallest when the rows are read from the last valid row up.
-    Classes are assumed to increase with depth, as everywhere in this module: no class-order permutation, no "background above and below" wrap.
+    Classes are assumed to increase with depth; a class order of its own, background above and below or lesion classes go through `layout_decode`.
     logits: fp32 / bf16 NHWC [B,H,W,C]; valid = (h_valid, w_valid), default the whole image, h_valid <= 4096.
     -> (mask uint8 [B,H,W], 0 outside the valid region; bnd int32 [B,C-1,W], the boundary rows of the mask (non-decreasing in k); changed int32 [B], the valid
     pixels whose class differs from the first argmax of q; best int32 [B,W] | None, the optimal total of each column).  Allocates its workspace, no sync."""
@@ -88,6 +148,57 @@ def ordered_decode(logits, n_class, valid=None, want_best=False):
     return mask, bnd, changed, best
 
 
+def layout_decode(pred, layout, valid=None, want_best=False, want_state=False):
+    """Layout decode (layout_decode.hip): per image and valid column the non-decreasing STATE sequence of `layout` that maximises the summed emissions
+    e(y, s) = max(q(y, layers[s]), max over the free classes of q(y, f)); the tie rule is `ordered_decode`'s.  A state shows its own class, or the best free
+    class where that scores higher.  pred: fp32 / bf16 logits NHWC [B,H,W,C] (q as in `ordered_decode`) or a uint8 class map [B,H,W] (labels, an argmax mask:
+    q = 256 on the pixel's class, 0 elsewhere); valid = (h_valid, w_valid), default the whole image, h_valid <= 4096.
+    -> (mask uint8 [B,H,W], 0 outside the valid region; bnd int32 [B,S-1,W], the row at which state k starts (non-decreasing in k); changed int32 [B], the valid
+    pixels whose class differs from the first argmax of q; best int32 [B,W] | None; state uint8 [B,H,W] | None).  Allocates its workspace, no sync.
+    With `Layout.identity(C)` every output equals `ordered_decode`'s."""
+    if not isinstance(layout, Layout):
+        raise TcctError(f'layout_decode: layout must be an evalm.Layout, got {type(layout).__name__}')
+    if not (torch.is_tensor(pred) and pred.is_cuda):
+        raise TcctError('layout_decode: the prediction must be a CUDA tensor (no CPU fallback)')
+    if pred.dtype not in _KIND:
+        raise TcctError(f'layout_decode: fp32 / bf16 logits [B,H,W,C] or uint8 classes [B,H,W] expected, got {pred.dtype}')
+    kind, C, S = _KIND[pred.dtype], layout.n_class, layout.n_states
+    if pred.dim() != (3 if kind == 2 else 4) or (kind != 2 and pred.shape[3] != C):
+        raise TcctError(f'layout_decode: prediction {tuple(pred.shape)} is neither NHWC [B,H,W,{C}] logits nor a uint8 [B,H,W] class map')
+    B, H, W = pred.shape[:3]
+    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    dev = pred.device
+    nbytes = lib.layout_decode_ws_bytes(B, H, W, S, len(layout.free))
+    if nbytes < 0:
+        raise TcctError(f'tcct_layout_decode_ws_bytes failed: {lib.last_error()}')
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    mask = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
+    bnd = torch.empty((B, S - 1, W), device=dev, dtype=torch.int32)
+    changed = torch.empty((B,), device=dev, dtype=torch.int32)
+    best = torch.empty((B, W), device=dev, dtype=torch.int32) if want_best else None
+    state = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if want_state else None
+    lib.layout_decode(pred.contiguous(), kind, B, H, W, C, layout._c_layers, S, layout.free_mask, hv, wv, ws, mask, bnd, changed, best, state)
+    return mask, bnd, changed, best, state
+
+
+def eval_layout_scores(counts, bnd_pred, bnd_lab, layout, valid, table=None, row=0):
+    """counts as `eval_counts` returns them (decoded mask against the label), bnd_pred / bnd_lab the surfaces `layout_decode` gives for prediction and label
+    -> fp64 [B, 2C + 2(S-1) + 1] = Dice_c | IoU_c | sum |d| per surface | sum d^2 per surface | n_col (include/tcct_hip.h).  `table`, `row` as `eval_scores`."""
+    B, C = counts.shape[0], counts.shape[1]
+    S, wid = layout.n_states, table_width(C, layout)
+    if C != layout.n_class or tuple(bnd_pred.shape) != tuple(bnd_lab.shape) or tuple(bnd_pred.shape[:2]) != (B, S - 1):
+        raise TcctError(f'eval_layout_scores: counts {tuple(counts.shape)}, surfaces {tuple(bnd_pred.shape)} / {tuple(bnd_lab.shape)} do not fit {layout!r}')
+    if table is None:
+        table, row = torch.empty((B, wid), device=counts.device, dtype=torch.float64), 0
+    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == wid and table.is_contiguous()):
+        raise TcctError(f'eval_layout_scores: table must be a contiguous CUDA fp64 [N, {wid}]')
+    if row < 0 or row + B > table.shape[0]:
+        raise TcctError(f'eval_layout_scores: rows {row}..{row + B} do not fit a table of {table.shape[0]} images')
+    out = table[row:row + B]
+    lib.eval_layout_scores(counts, bnd_pred.contiguous(), bnd_lab.contiguous(), B, C, S, bnd_pred.shape[2], int(valid[0]), int(valid[1]), out)
+    return out
+
+
 def eval_scores(counts, bnd_pred, bnd_lab, valid, table=None, row=0):
     """counts / bnd_* as eval_counts returns them, valid = (h_valid, w_valid) -> fp64 [B, 4C-1] (module docstring of eval.hip / include/tcct_hip.h for the
     columns).  With `table` (fp64 [N, 4C-1], contiguous) the rows go to table[row : row + B] and that slice is returned."""
@@ -107,22 +218,23 @@ def eval_scores(counts, bnd_pred, bnd_lab, valid, table=None, row=0):
     return out
 
 
-def aggregate(table, n_class):
+def aggregate(table, n_class, layout=None):
     """per-image table (CPU tensor or numpy, [N, 4C-1]) -> dict: `dice`, `iou` [C] (means over images), `val_f1s` / `val_iou` (their means over classes 1..C-1,
     what KiteSeg.val() reports), `mad`, `rmse` [C-1] in pixels pooled over the annotated columns of all images (NaN when there is none), `mad_mean`,
-    `n_images`, `n_columns`, `table`"""
+    `n_images`, `n_columns`, `table`.  With a `layout` the table is `eval_layout_scores`' [N, 2C + 2(S-1) + 1] and `mad`, `rmse` have one entry per surface."""
     C = n_class
-    t = np.asarray(table.detach().cpu().numpy() if torch.is_tensor(table) else table, dtype=np.float64).reshape(-1, table_width(C))
+    nb = C - 1 if layout is None else layout.n_states - 1
+    t = np.asarray(table.detach().cpu().numpy() if torch.is_tensor(table) else table, dtype=np.float64).reshape(-1, table_width(C, layout))
     n = t.shape[0]
     nan = np.full(C, np.nan)
     dice = t[:, :C].mean(0) if n else nan.copy()
     iou = t[:, C:2 * C].mean(0) if n else nan.copy()
-    ncol = float(t[:, 4 * C - 2].sum())
-    sabs, ssq = t[:, 2 * C:3 * C - 1].sum(0), t[:, 3 * C - 1:4 * C - 2].sum(0)
+    ncol = float(t[:, 2 * C + 2 * nb].sum())
+    sabs, ssq = t[:, 2 * C:2 * C + nb].sum(0), t[:, 2 * C + nb:2 * C + 2 * nb].sum(0)
     if ncol > 0:
         mad, rmse = sabs / ncol, np.sqrt(ssq / ncol)
     else:
-        mad, rmse = np.full(C - 1, np.nan), np.full(C - 1, np.nan)
+        mad, rmse = np.full(nb, np.nan), np.full(nb, np.nan)
     return {'dice': dice, 'iou': iou, 'val_f1s': float(dice[1:].mean()), 'val_iou': float(iou[1:].mean()), 'mad': mad, 'rmse': rmse,
             'mad_mean': float(mad.mean()), 'n_images': int(n), 'n_columns': int(ncol), 'table': t}
 
@@ -150,27 +262,32 @@ def metrics_dict(res):
     return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res.items() if k != 'table'}
 
 
-def per_image_header(n_class):
+def per_image_header(n_class, layout=None):
     C = n_class
-    return ([f'dice_{c}' for c in range(C)] + [f'iou_{c}' for c in range(C)] + [f'sum_abs_{k}' for k in range(1, C)] + [f'sum_sq_{k}' for k in range(1, C)]
+    nb = C if layout is None else layout.n_states
+    return ([f'dice_{c}' for c in range(C)] + [f'iou_{c}' for c in range(C)] + [f'sum_abs_{k}' for k in range(1, nb)] + [f'sum_sq_{k}' for k in range(1, nb)]
             + ['n_col'])
 
 
 class Evaluator:
     """Scores of up to `n_images` images in a preallocated device table.  `add` launches the two kernels (and the fill of their workspace) and never syncs;
-    `result` makes ONE device -> host copy and aggregates on the host."""
+    `result` makes ONE device -> host copy and aggregates on the host.  With a `layout` `add(..., decode='ordered')` runs prediction and label
+    through `layout_decode`, scores Dice / IoU of the decoded mask and the surface errors between the two decodes; the table then is `eval_layout_scores`'."""
 
-    def __init__(self, n_images, n_class, device):
+    def __init__(self, n_images, n_class, device, layout=None):
         if n_images < 1 or not 2 <= n_class <= 16:
             raise TcctError(f'Evaluator: n_images={n_images}, n_class={n_class} (2..16)')
-        self.n_class, self.capacity, self.n = n_class, int(n_images), 0
-        self.table = torch.zeros((self.capacity, table_width(n_class)), device=device, dtype=torch.float64)
+        if layout is not None and (not isinstance(layout, Layout) or layout.n_class != n_class):
+            raise TcctError(f'Evaluator: layout={layout!r} does not describe {n_class} classes')
+        self.n_class, self.capacity, self.n, self.layout = n_class, int(n_images), 0, layout
+        self.table = torch.zeros((self.capacity, table_width(n_class, layout)), device=device, dtype=torch.float64)
         self.decode, self.changed = 'argmax', None
 
     def add(self, pred, lab, valid=None, want_mask=False, decode='argmax'):
         """one batch; -> the scored mask uint8 [B,H,W] (device) when `want_mask`, else None.  decode='argmax': the per-pixel first maximum of the logits;
         'ordered': the logits go through `ordered_decode` first and its mask is what is scored (and returned); all batches of one Evaluator decode alike"""
         check_decode(decode)
+        check_layout_decode(self.layout, decode)
         B, H, W = lab.shape
         if self.n + B > self.capacity:
             raise TcctError(f'Evaluator: {self.n} + {B} images exceed the {self.capacity} it was made for')
@@ -182,21 +299,33 @@ class Evaluator:
             _check(pred, lab, self.n_class, valid)
             if pred.dtype == torch.uint8:
                 raise TcctError("Evaluator: decode='ordered' needs logits, not a uint8 class mask")
-            omask, _, changed, _ = ordered_decode(pred, self.n_class, valid)
+            if self.layout is not None:
+                omask, bp, changed, _, _ = layout_decode(pred, self.layout, valid)
+                bl = layout_decode(lab.contiguous(), self.layout, valid)[1]     # the label's surfaces: the label through the same decode
+            else:
+                omask, _, changed, _ = ordered_decode(pred, self.n_class, valid)
             if self.changed is None:
                 self.changed = torch.zeros((), device=changed.device, dtype=torch.int64)
             self.changed += changed.sum()                   # stays on the device
-            counts, bp, bl, _ = eval_counts(omask, lab, self.n_class, valid)
+            if self.layout is not None:
+                counts = eval_counts(omask, lab, self.n_class, valid, want_boundaries=False)[0]
+            else:
+                counts, bp, bl, _ = eval_counts(omask, lab, self.n_class, valid)
             mask = omask if want_mask else None
         else:
             counts, bp, bl, mask = eval_counts(pred, lab, self.n_class, valid, want_mask=want_mask)
-        eval_scores(counts, bp, bl, valid, table=self.table, row=self.n)
+        if self.layout is not None:
+            eval_layout_scores(counts, bp, bl, self.layout, valid, table=self.table, row=self.n)
+        else:
+            eval_scores(counts, bp, bl, valid, table=self.table, row=self.n)
         self.n += B
         return mask
 
     def result(self):
-        res = aggregate(self.table[:self.n].cpu(), self.n_class)
+        res = aggregate(self.table[:self.n].cpu(), self.n_class, self.layout)
         if self.decode == 'ordered':
             res['decode'] = 'ordered'
             res['changed_pixels'] = int(self.changed.item()) if self.changed is not None else 0
+        if self.layout is not None:
+            res['layers'], res['free'] = list(self.layout.layers), list(self.layout.free)
         return res

@@ -6,13 +6,25 @@ Takes the flags of kite/main.py that build the dataset and the network (--db --n
   --ckpt FILE   a state_dict `.pt` or a checkpoint `.npz`, loaded with checkpoint.load_reference_checkpoint: a layout or class-count mismatch raises
                 instead of scoring randomly initialised heads (default: ROOT/val_top.pt, what fit() writes)
   --split       val | test | train          --val_bs  images per batch          --out DIR  masks as PNG (gray = class x 30), metrics.json, per_image.csv
-  --decode      argmax (default) | ordered: score and write the masks of evalm.ordered_decode, classes non-decreasing down every column"""
+  --decode      argmax (default) | ordered: score and write the masks of evalm.ordered_decode, classes non-decreasing down every column
+  --layers      with --decode=ordered: the classes of the column states from top to bottom, e.g. 0,1,2,3,4,5,6,7,8,0 for a set whose class 0 lies above AND
+                below the retina; --free=9 names classes that are no layer (fluid, lesions).  Prediction and label then go through evalm.layout_decode and
+                MAD / RMSE are listed per surface `class above|class below`.  Default: the layout the dataset file stores (pack_dataset.py
+                --layers / --free), else none"""
 import argparse
 import os
 
 import torch
 
 from .main import str2bool, int_pair, parse_args as train_args
+
+
+def class_ids(s):
+    """'0,1,2,0' -> [0, 1, 2, 0]"""
+    try:
+        return [int(v) for v in s.split(',') if v.strip() != '']
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'{s!r}: comma-separated class ids expected')
 
 
 def build_parser():
@@ -30,6 +42,9 @@ def build_parser():
     p.add_argument('--val_bs', type=int, default=8, help='images per evaluation batch')
     p.add_argument('--out', type=str, default='', help='folder for the predicted masks, metrics.json and per_image.csv')
     p.add_argument('--decode', type=str, default='argmax', choices=['argmax', 'ordered'], help='per-pixel argmax, or the ordered layer decode (DESIGN 6c)')
+    p.add_argument('--layers', type=class_ids, default=None, help='with --decode=ordered: classes of the column states from top to bottom, e.g. 0,1,2,3,4,5,6,7,8,0 '
+                   '(class 0 above and below the retina; DESIGN 6d); default: the layout stored in the dataset file, else classes increase with depth')
+    p.add_argument('--free', type=class_ids, default=None, help='with --layers: classes that are no layer (fluid, lesions), e.g. 9')
     p.add_argument('--bug', type=str2bool, default=False, help='Debug Mode: ten batches')
     return p
 
@@ -42,6 +57,10 @@ def parse_args(argv=None):
         raise SystemExit(f'--att={args.att} is only offered for --net=stc_tt')
     if args.val_bs < 1:
         raise SystemExit(f'--val_bs={args.val_bs}')
+    if args.free is not None and args.layers is None:
+        raise SystemExit('--free needs --layers')
+    if args.layers is not None and args.decode != 'ordered':
+        raise SystemExit('--layers describes the ordered decode: pass --decode=ordered')
     return args
 
 
@@ -52,11 +71,14 @@ def report(res):
              'class    ' + ' '.join(f'{c:>7d}' for c in range(C)) + '   mean(1..)',
              'Dice     ' + ' '.join(f'{v:7.4f}' for v in res['dice']) + f"   {res['val_f1s']:.4f}",
              'IoU      ' + ' '.join(f'{v:7.4f}' for v in res['iou']) + f"   {res['val_iou']:.4f}",
-             'boundary ' + ' '.join(f'{k:>7d}' for k in range(1, C)) + '   mean',
+             ('surface  ' + ' '.join(f'{a}|{b}'.rjust(7) for a, b in zip(res['layers'], res['layers'][1:])) if 'layers' in res else
+              'boundary ' + ' '.join(f'{k:>7d}' for k in range(1, C))) + '   mean',
              'MAD px   ' + ' '.join(f'{v:7.3f}' for v in res['mad']) + f"   {res['mad_mean']:.3f}",
              'RMSE px  ' + ' '.join(f'{v:7.3f}' for v in res['rmse'])]
     if 'decode' in res:
         lines.append(f"decode   {res['decode']}: {res['changed_pixels']} pixels differ from the per-pixel argmax")
+    if 'layers' in res:
+        lines.append(f"layout   layers {','.join(map(str, res['layers']))}" + (f", free {','.join(map(str, res['free']))}" if res['free'] else ''))
     return '\n'.join(lines)
 
 
@@ -84,7 +106,11 @@ def main(argv=None):
     ckpt = args.ckpt or os.path.join(keras.root, 'val_top.pt')
     missing, unexpected = load_reference_checkpoint(keras.model, ckpt)
     print(f'loaded model: {ckpt} ({len(missing)} missing, {len(unexpected)} unexpected keys)')
-    res = keras.evaluate(split=args.split, bs=args.val_bs, out_dir=args.out or None, decode=args.decode)
+    layout = None               # None: KiteSeg.evaluate takes the dataset's own layout under --decode=ordered
+    if args.layers is not None:
+        from ..evalm import Layout
+        layout = Layout(args.layers, args.free or (), dataset.out_channels)
+    res = keras.evaluate(split=args.split, bs=args.val_bs, out_dir=args.out or None, decode=args.decode, layout=layout)
     print(report(res))
     return res
 

@@ -50,12 +50,14 @@ class KiteSeg(KiteBack):
             base.eager_feats = udh and os.environ.get('TCCT_EAGER_FEATS', '1') != '0'
             base.compose_heads = not udh
 
-    def predict(self, img, softmax=True, *args, decode='argmax'):
+    def predict(self, img, softmax=True, *args, decode='argmax', layout=None):
         """reference loop_seg.py:21-33: one_hot(argmax(softmax(out[0]))).  Returns a lazy MaskOneHot (class-index map;
         `.dense()` gives the reference's float [B,C,H,W]) when softmax=True, else the raw logits.  decode='ordered' (with softmax=True): the mask is
-        `evalm.ordered_decode`'s, classes non-decreasing down every column, instead of the per-pixel argmax; the hipGraph replay is not used then."""
-        from ..evalm import check_decode
+        `evalm.ordered_decode`'s, classes non-decreasing down every column, instead of the per-pixel argmax; the hipGraph replay is not used then.
+        `layout` (an `evalm.Layout`, with decode='ordered'): the mask is `evalm.layout_decode`'s instead."""
+        from ..evalm import check_decode, check_layout_decode
         ordered = check_decode(decode) == 'ordered'
+        check_layout_decode(layout, decode)
         with torch.no_grad():
             img = self.cuda(img)
             if softmax and not ordered and self.use_graph and not self.model.training and img.is_cuda and img.shape[0] <= 2:
@@ -80,7 +82,10 @@ class KiteSeg(KiteBack):
             if softmax:
                 lg = as_nhwc(pred)
                 B, H, W, C = lg.shape
-                if ordered:
+                if ordered and layout is not None:
+                    from ..evalm import layout_decode
+                    idx = layout_decode(lg, layout)[0]
+                elif ordered:
                     from ..evalm import ordered_decode
                     idx = ordered_decode(lg, C)[0]
                 else:
@@ -148,20 +153,26 @@ class KiteSeg(KiteBack):
             return ds.testSet(bs=bs)
         raise TcctError(f"evaluate(split={split!r}): this dataset has no evalSet(); only 'val' and 'test' are available")
 
-    def evaluate(self, split='val', bs=8, out_dir=None, flagDebug=False, decode='argmax'):
+    def evaluate(self, split='val', bs=8, out_dir=None, flagDebug=False, decode='argmax', layout=None):
         """Scores of a whole split in batches (tcct_amd/evalm.py): per-class Dice / IoU and per-boundary MAD / RMSE of the valid region (the image before
         `parse` padded it).  Eval mode, no gradients, main head only; the logits go straight to the counting kernel and nothing is read back before the end
         -- unless `out_dir` is given: then the mask of every batch is copied to the host and written as `{split}_{index:05d}.png` (gray = class x 30, cropped
         to the valid region), next to `metrics.json` and `per_image.csv`.  Returns the dict of `evalm.aggregate` (`val_f1s` / `val_iou` as `val()` defines them).
         decode='ordered': the logits of every batch go through `evalm.ordered_decode` (classes non-decreasing down every column of the valid region) and that
-        mask is what is scored and written; the result and `metrics.json` then also carry `decode` and `changed_pixels` (pixels that differ from the argmax)."""
+        mask is what is scored and written; the result and `metrics.json` then also carry `decode` and `changed_pixels` (pixels that differ from the argmax).
+        `layout` (an `evalm.Layout`, with decode='ordered'; default: the dataset's `.layout`, if its file stores one): prediction and label go through
+        `evalm.layout_decode` (background above and below, lesion classes), MAD / RMSE are those of the S-1 surfaces between the layout's states,
+        and the result also carries `layers` and `free`."""
         import os
         from .. import evalm
         evalm.check_decode(decode)
         from ..nets.reg import as_label_index
+        if layout is None and decode == 'ordered':
+            layout = getattr(self.dataset, 'layout', None)
         batches = self._eval_batches(split, bs)
         n_max = int(getattr(batches, 'n_images', len(batches) * bs))
-        ev = evalm.Evaluator(max(n_max, 1), self.NB_CLASS, self.device)
+        evalm.check_layout_decode(layout, decode)
+        ev = evalm.Evaluator(max(n_max, 1), self.NB_CLASS, self.device, layout=layout)
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
         prev = torch.is_grad_enabled()
@@ -189,7 +200,7 @@ class KiteSeg(KiteBack):
             import json
             with open(os.path.join(out_dir, 'metrics.json'), 'w') as f:
                 json.dump(evalm.metrics_dict(res), f, indent=1)
-            np.savetxt(os.path.join(out_dir, 'per_image.csv'), res['table'], delimiter=',', header=','.join(evalm.per_image_header(self.NB_CLASS)), comments='',
+            np.savetxt(os.path.join(out_dir, 'per_image.csv'), res['table'], delimiter=',', header=','.join(evalm.per_image_header(self.NB_CLASS, layout)), comments='',
                        fmt='%.17g')
         return res
 

@@ -56,9 +56,25 @@ def pack_split(folder, split, rows):
     return np.stack(imgs), np.stack(labs)
 
 
-def pack(folder, out, db='goals'):
+def check_layout(layers, free, n_class):
+    """the rules of tcct_amd.evalm.Layout, so that a file that cannot be loaded is not written"""
+    layers, free = [int(c) for c in layers], sorted(int(c) for c in (free or ()))
+    if not 2 <= len(layers) <= 16 or any(a == b for a, b in zip(layers, layers[1:])):
+        raise SystemExit(f'--layers={layers}: 2..16 states, neighbours of different classes')
+    if set(layers) & set(free) or len(set(free)) != len(free) or set(layers) | set(free) != set(range(n_class)):
+        raise SystemExit(f'--layers={layers} --free={free}: every class of 0..{n_class - 1} must be a layer or free, and not both')
+    return np.asarray(layers, dtype=np.int64), np.asarray(free, dtype=np.int64)
+
+
+def pack(folder, out, db='goals', layers=None, free=None):
     rows = ROWS.get(db, ROWS_DEFAULT)
     arrays = {'n_class': np.int64(N_CLASS.get(db, N_CLASS_DEFAULT))}
+    if layers is not None:
+        # a lesion class beyond the dataset's layer classes (--free=9 on a 9-class set) raises the class count
+        arrays['n_class'] = np.int64(max([int(arrays['n_class'])] + [int(c) + 1 for c in list(layers) + list(free or ())]))
+        arrays['layers'], arrays['free'] = check_layout(layers, free, int(arrays['n_class']))
+    elif free:
+        raise SystemExit('--free needs --layers')
     for split in ('train', 'val', 'test'):
         got = pack_split(folder, split, rows)
         if got is not None:
@@ -74,8 +90,12 @@ def main(argv=None):
     ap.add_argument('folder')
     ap.add_argument('out')
     ap.add_argument('--db', default='goals', help='dataset name: selects the row range and the class count (heg, duke, duke1..3, hcms, hcms1, goals; others: rows 0:992, 8 classes)')
+    ids = lambda s: [int(v) for v in s.split(',') if v.strip() != '']              # noqa: E731
+    ap.add_argument('--layers', type=ids, default=None, help='classes of the column states from top to bottom, e.g. 0,1,2,3,4,5,6,7,8,0 when class 0 lies above '
+                    'and below the retina; stored as `layers` (the layout of the ordered decode, DESIGN 6d); default: not stored, classes increase with depth')
+    ap.add_argument('--free', type=ids, default=None, help='with --layers: classes that are no layer (fluid, lesions), e.g. 9; stored as `free`')
     a = ap.parse_args(argv)
-    for k, v in pack(a.folder, a.out, a.db).items():
+    for k, v in pack(a.folder, a.out, a.db, a.layers, a.free).items():
         print(k, v)
 
 
