@@ -688,6 +688,28 @@ int tcct_layout_decode(const void* pred, int kind, int B, int H, int W, int C, c
  * and bnd_lab[b][0][x] < h_valid; int64 sums, converted once. */
 int tcct_eval_layout_scores(const int32_t* counts, const int32_t* bnd_pred, const int32_t* bnd_lab, int B, int C, int S, int W, int h_valid, int w_valid,
                             double* table, tcct_stream_t stream);
+/* Layout marginals (layout_marginals.hip; evalm.layout_marginals): sum-product where tcct_layout_decode is max-product.  logits: kind 0 = fp32 NHWC
+ * [B,H,W,C], 1 = bf16 (widened exactly); a class map (kind 2) is refused.  layers, S, free_mask as tcct_layout_decode; tau > 0 is the softmax temperature.
+ * Per image and column x < w_valid, over the rows y < h_valid: s(y,c) = clamp(logit, -1024, 1024) (NaN -> -1024); p = softmax_c(s / tau), row maximum
+ * subtracted; p~ = max(p, 2^-40); E(y,s) = p~(y,layers[s]) + sum over the free classes of p~(y,f).  A non-decreasing state sequence weighs prod_y E(y,s(y)),
+ * any start state is allowed; gamma_y(s) is the share of the sequences with s(y) = s and G_k(y) = min(sum_{s<k} gamma_y(s), 1), a running sum over s.
+ *   surf   fp32 [B,S-1,W]    sum_y G_k(y), k = 1..S-1: the expected row at which state k starts (the expectation of tcct_layout_decode's bnd), non-decreasing
+ *                            in k, in [0, h_valid]
+ *   var    fp32 [B,S-1,W]    max(sum_y (2y+1) G_k(y) - surf_k^2, 0): the variance of that row in px^2
+ *   logz   fp32 [B,W]        the log of the summed weights of the column
+ *   post   fp32 [B,H,W,C]    (nullable) sum_{s: layers[s]=c} gamma_y(s) p~(y,c) / E(y,s) for a layer class, p~(y,f) sum_s gamma_y(s) / E(y,s) for a free class:
+ *                            sums to 1 over c; every pixel is written, 0 outside the valid region
+ * surf, m2 and logz are accumulated in fp64, the rest is fp32.  Columns x >= w_valid read 0 in every output; h_valid == 0 or w_valid == 0 zeroes every output
+ * without a launch.  No atomics: every output is a plain store by the lane that owns the column.  ws: tcct_layout_marginals_ws_bytes(B,H,W,S,n_free) bytes.
+ * Limits are tcct_layout_decode's: C in 2..16, S in 2..16, h_valid <= min(H, 4096), w_valid <= W, B <= 65535, H*W*C*4 < 2^31. */
+int64_t tcct_layout_marginals_ws_bytes(int B, int H, int W, int S, int n_free);
+int tcct_layout_marginals(const void* logits, int kind, int B, int H, int W, int C, const int* layers, int S, int free_mask, int h_valid, int w_valid, float tau,
+                          void* ws, float* surf, float* var, float* logz, float* post, tcct_stream_t stream);
+/* The expected surfaces against the label's integer ones: surf, var fp32 [B,S-1,W] of tcct_layout_marginals, bnd_lab int32 [B,S-1,W] of tcct_layout_decode of the
+ * label.  table fp64 [B, 3(S-1) + 1]: [0,S-1) sum_x |surf - bnd_lab| per surface; [S-1, 2(S-1)) sum_x (surf - bnd_lab)^2; [2(S-1), 3(S-1)) sum_x var; last
+ * n_col.  Annotated columns as tcct_eval_layout_scores: x < w_valid and bnd_lab[b][0][x] < h_valid.  One block per image, fp64, a fixed reduction order. */
+int tcct_eval_soft_scores(const float* surf, const float* var, const int32_t* bnd_lab, int B, int S, int W, int h_valid, int w_valid, double* table,
+                          tcct_stream_t stream);
 
 /* ---- boundary-regression loss pieces (RegNet.regular_reg, nets/reg.py:109-156); this pipeline is fp32 -------- */
 int tcct_slice_channels_fwd(const void* x, float* y, int64_t M, int C, int start, int n, int dtype, tcct_stream_t stream);

@@ -1,0 +1,453 @@
+// Layout marginals: sum-product over the column model of layout_decode.hip.  Per image and valid column, over the rows y < h_valid:
+//   s(y,c) = clamp(logit, -1024, 1024) (NaN -> -1024);  p = softmax_c(s / tau), row maximum subtracted;  p~ = max(p, 2^-40)
+//   E(y,s) = p~(y, layers[s]) + sum over the free classes f of p~(y,f)
+//   the weight of a non-decreasing state sequence s(0) <= .. <= s(h-1) is prod_y E(y, s(y)); any start state is allowed (6d: D_-1 = 0)
+//   logz = log of the summed weights;  gamma_y(s) = the share of the sequences with s(y) = s;  G_k(y) = sum_{s<k} gamma_y(s)  (a running prefix sum, min 1)
+//   surf_k = sum_y G_k(y)   the expected row at which state k starts;   var_k = max(sum_y (2y+1) G_k(y) - surf_k^2, 0)   its variance in px^2
+//   post(y,c) = sum_{s: layers[s]=c} gamma_y(s) p~(y,c) / E(y,s)  for a layer class,  p~(y,f) sum_s gamma_y(s) / E(y,s)  for a free class
+//
+// The forward variables alpha_y(s) = E(y,s) sum_{s'<=s} alpha_{y-1}(s') are NOT kept as one fp32 vector per row with a common scale: two states can see the
+// same evidence for hundreds of rows (0,1,..,C-1,0: background above and below) while every pixel that contradicts one of them costs it 2^-40, so the ratio
+// of two alphas leaves the fp32 (and, from 27 such pixels on, the fp64) range although only LATER rows decide between them.  What is kept instead, with
+// c_y(s) = sum_{s'<=s} alpha_y(s'):
+//   N_y(s)   = c_y(s) / c_{y-1}(s) = E(y,s) + rho_{y-1}(s) N_y(s-1)            in [2^-40, 32]: one fma per state, the chain of the walk
+//   u_y(s)   = alpha_y(s) / c_y(s) = E(y,s) / N_y(s)                            in [0, 1]
+//   rho_y(s) = c_y(s-1) / c_y(s)   = rho_{y-1}(s) N_y(s-1) / N_y(s) = 1 - u_y(s)   as an fp32 mantissa in [0.5, 1) and an int32 exponent; rho_{-1} = 1
+//   logz = sum_y log N_y(S-1)      (1 / N_y(S-1) is the per-row scale of the textbook recursion)
+// The scaled alpha of the textbook form is u_y(s) prod_{j>s} rho_y(j).  Given s(y+1) = s' the state s(y) = s <= s' has probability alpha_y(s) / c_y(s') =
+// u_y(s) prod_{s<j<=s'} rho_y(j), whatever the later rows show, so the backward walk needs no second set of variables:
+//   Q(s) = gamma_{y+1}(s) + rho_y(s+1) Q(s+1);   gamma_y(s) = u_y(s) Q(s), divided by their sum;   "gamma_h" = all mass on the last state
+// A rho that underflows fp32 here is a share below 2^-149 of the sequences through s(y+1) = s'.  The workspace holds per pixel and state s >= 1 ONE float:
+// rho when rho < 0.5, else -u (the sign bit is the tag, so a -0 is u = 0), so that the small one of the pair is the stored one; state 0 has rho = 0, u = 1.
+//
+// Schedule: k_layout_decode's.  A wave owns 64 adjacent columns of one image, a lane owns a column; row addresses are clamped, not guarded; two row batches
+// alternate so that the loads of the next are in flight under the chain of the current one; the layout is wave-uniform (scalar registers), state s loads ITS
+// class from a uniform base.  States >= S are padding with E = 0 (so N(s) = N(S-1), u = 0, rho = 1: they carry nothing and pass everything through), free
+// slots >= n_free re-read the last free class with weight 0.  The softmax denominator counts every class once: the first state of a class and every real
+// free slot.  surf, m2 and logz are accumulated per lane in fp64 (m2 - surf^2 cancels); everything else is fp32.  No atomics: two calls give the same bits.
+#include "common.h"
+#include <type_traits>
+
+#define MARG_FLOOR 9.094947017729282e-13f      // 2^-40
+struct MargArgs { int cls[16]; int fcls[14]; };
+// rows per batch, both walks; halved where the posterior or 14 free slots fill the registers (the emissions of a whole batch are computed ahead of its chain)
+template <int MAXS, int NF, bool POST> struct MargCfg {
+    static constexpr int R = POST && NF > 2 ? (MAXS <= 10 ? 2 : 1) : (MAXS <= 8 ? 8 : 4) / (POST || NF > 2 ? 2 : 1);
+};
+static inline int marg_maxs(int S) { return S <= 5 ? 5 : (S <= 6 ? 6 : (S <= 10 ? 10 : 16)); }
+
+// the loaded bits as they are: a bf16 value is widened where it is used, not where it is loaded, so that a batch of loads needs no wait of its own
+template <int MAXS, int NF> struct MargRow {
+    uint32_t z[MAXS];               // the logit of every state's class
+    uint32_t zf[NF ? NF : 1];       // ... of every free slot
+};
+__device__ __forceinline__ uint32_t marg_ldraw(const float* p) { return __float_as_uint(*p); }
+__device__ __forceinline__ uint32_t marg_ldraw(const bf16* p) { return (uint32_t)*(const uint16_t*)p; }
+template <int KIND> __device__ __forceinline__ float marg_val(uint32_t raw) { return __uint_as_float(KIND == 1 ? raw << 16 : raw); }
+// a false comparison yields the lower clamp (NaN -> -1024), as decode.hip's decode_quant
+__device__ __forceinline__ float marg_clamp(float s) {
+    const float t = s > -1024.f ? s : -1024.f;
+    return t < 1024.f ? t : 1024.f;
+}
+
+// p~ of every state's class (pl), of every free slot (pf, 0 for a padded slot) and the emissions (0 for a padded state)
+template <int MAXS, int KIND, int NF>
+__device__ __forceinline__ void marg_emissions(const MargRow<MAXS, NF>& rw, float inv_tau, int first_mask, int S, int n_free, float (&E)[MAXS], float (&pl)[MAXS],
+                                               float (&pf)[NF ? NF : 1]) {
+    float t[MAXS], tf[NF ? NF : 1], mx;
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s) {
+        t[s] = marg_clamp(marg_val<KIND>(rw.z[s])) * inv_tau;
+        mx = s == 0 ? t[0] : fmaxf(mx, t[s]);
+    }
+    if constexpr (NF > 0) {
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            tf[j] = marg_clamp(marg_val<KIND>(rw.zf[j])) * inv_tau;
+            mx = fmaxf(mx, tf[j]);
+        }
+    }
+    float den = 0.f;
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s) {
+        t[s] = expf(t[s] - mx);
+        den += ((first_mask >> s) & 1) ? t[s] : 0.f;
+    }
+    if constexpr (NF > 0) {
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            tf[j] = expf(tf[j] - mx);
+            den += j < n_free ? tf[j] : 0.f;
+        }
+    }
+    const float inv = 1.f / den;            // den >= 1: the class of the maximum counts once
+    float F = 0.f;
+    if constexpr (NF > 0) {
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            pf[j] = j < n_free ? fmaxf(tf[j] * inv, MARG_FLOOR) : 0.f;
+            F += pf[j];
+        }
+    } else pf[0] = 0.f;
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s) {
+        pl[s] = fmaxf(t[s] * inv, MARG_FLOOR);
+        E[s] = s < S ? pl[s] + F : 0.f;
+    }
+}
+
+// KIND: 0 fp32 logits, 1 bf16 logits.  NF: free-class slots (0: the layout has none).  POST: the per-pixel class posterior is written
+template <int MAXS, int KIND, int NF, bool POST>
+__global__ void __launch_bounds__(64) k_layout_marginals(const void* __restrict__ logits, int H, int W, int C, const MargArgs L, int S, int first_mask, int n_free,
+                                                         int h_valid, int w_valid, float inv_tau, float* __restrict__ ws, float* __restrict__ surf,
+                                                         float* __restrict__ var, float* __restrict__ logz, float* __restrict__ post) {
+    constexpr int R = MargCfg<MAXS, NF, POST>::R, NV = MAXS - 1;
+    typedef typename std::conditional<KIND == 1, bf16, float>::type T;
+    typedef MargRow<MAXS, NF> Row;
+    const int lane = threadIdx.x, b = blockIdx.z;
+    const int x = blockIdx.x * 64 + lane;
+    if (x >= W) return;
+    const int64_t pix0 = (int64_t)b * H * W + x;            // pixel (b, 0, x); row y is pix0 + y * W
+    if (x >= w_valid) {
+        // a padded column: every output reads 0
+        for (int k = 1; k < S; ++k) {
+            surf[((int64_t)b * (S - 1) + k - 1) * W + x] = 0.f;
+            var[((int64_t)b * (S - 1) + k - 1) * W + x] = 0.f;
+        }
+        logz[(int64_t)b * W + x] = 0.f;
+        if constexpr (POST)
+            for (int y = 0; y < H; ++y)
+                for (int c = 0; c < C; ++c) post[(pix0 + (int64_t)y * W) * C + c] = 0.f;
+        return;
+    }
+    // image base (uniform) + class (uniform) + pixel offset (32 bits per lane: H * W * C * 4 < 2^31 is checked by the caller).  Every row address is clamped
+    // into the valid rows, so no load sits behind a branch; a row outside re-reads the nearest one and is not used.
+    const int esz = (int)sizeof(T) * C;
+    const char* img = (const char*)logits + (int64_t)b * H * W * esz;
+    const uint32_t col_off = (uint32_t)x * (uint32_t)esz, rsb = (uint32_t)W * (uint32_t)esz;
+    auto load_row = [&](Row& rw, int y) {
+        const uint32_t off = (uint32_t)min(max(y, 0), h_valid - 1) * rsb + col_off;
+#pragma unroll
+        for (int s = 0; s < MAXS; ++s) rw.z[s] = marg_ldraw((const T*)((const char*)((const T*)img + L.cls[s]) + off));
+        if constexpr (NF > 0) {
+#pragma unroll
+            for (int j = 0; j < NF; ++j) rw.zf[j] = marg_ldraw((const T*)((const char*)((const T*)img + L.fcls[j]) + off));
+        }
+    };
+    float* __restrict__ wcol = ws + (int64_t)b * H * NV * W + x;       // value (y, s >= 1) of this column is wcol[(y * NV + s - 1) * W]
+    // ---------------------------------------------------------------- forward: N, rho (mantissa, exponent), the stored rho | -u, logz
+    float rm[MAXS], rho[MAXS];
+    int rk[MAXS];
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s) { rm[s] = 0.5f; rk[s] = 1; rho[s] = 1.f; }
+    double lz = 0.0;
+    auto row = [&](const Row& rw, int y) {
+        float E[MAXS], pl[MAXS], pf[NF ? NF : 1], N[MAXS];
+        marg_emissions<MAXS, KIND, NF>(rw, inv_tau, first_mask, S, n_free, E, pl, pf);
+        N[0] = E[0];
+#pragma unroll
+        for (int s = 1; s < MAXS; ++s) N[s] = fmaf(rho[s], N[s - 1], E[s]);
+#pragma unroll
+        for (int s = 1; s < MAXS; ++s) {
+            const float rn = __builtin_amdgcn_rcpf(N[s]);
+            const float u = E[s] * rn;
+            const float mn = rm[s] * (N[s - 1] * rn);       // in [2^-47, 2^46]: N in [2^-40, 32]
+            rk[s] += __builtin_amdgcn_frexp_expf(mn);
+            rm[s] = __builtin_amdgcn_frexp_mantf(mn);
+            const float raw = ldexpf(rm[s], rk[s]);
+            if (!(raw < 1.f) || s >= S) { rm[s] = 0.5f; rk[s] = 1; }       // rho <= 1 (rounding may say otherwise); a padded state passes everything through
+            rho[s] = s < S ? fminf(raw, 1.f) : 1.f;
+            wcol[((int64_t)y * NV + s - 1) * W] = rho[s] < 0.5f ? rho[s] : -u;
+        }
+        lz += (double)logf(N[MAXS - 1]);
+    };
+    {
+        Row za[R], zb[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) load_row(za[r], r);
+        int y0 = 0;
+        // whole batches, two per trip: the batches change places instead of being copied (6d)
+        for (; y0 + 2 * R <= h_valid; y0 += 2 * R) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) load_row(zb[r], y0 + R + r);
+            // the loads stay in front of the other batch's arithmetic: in <5, bf16, 0 free, no post> hipcc sank every 16-bit load to its first use and waited
+            // for it there (80 x s_waitcnt vmcnt(0) per trip, 1.7 x the time of the fp32 kernel)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) row(za[r], y0 + r);
+#pragma unroll
+            for (int r = 0; r < R; ++r) load_row(za[r], y0 + 2 * R + r);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) row(zb[r], y0 + R + r);
+        }
+        if (y0 + R <= h_valid) {                        // one more whole batch (wave-uniform)
+#pragma unroll
+            for (int r = 0; r < R; ++r) load_row(zb[r], y0 + R + r);
+#pragma unroll
+            for (int r = 0; r < R; ++r) row(za[r], y0 + r);
+#pragma unroll
+            for (int r = 0; r < R; ++r) za[r] = zb[r];
+            y0 += R;
+        }
+#pragma unroll
+        for (int r = 0; r < R - 1; ++r)
+            if (y0 + r < h_valid) row(za[r], y0 + r);   // the last, partial batch (wave-uniform)
+    }
+    logz[(int64_t)b * W + x] = (float)lz;
+    // ---------------------------------------------------------------- backward: gamma, the surfaces' moments in fp64, the posterior
+    struct Back { float v[NV]; };
+    auto load_back = [&](Back& bk, int y) {
+        const int64_t o = (int64_t)max(y, 0) * NV * W;
+#pragma unroll
+        for (int s = 1; s < MAXS; ++s) bk.v[s - 1] = wcol[o + (int64_t)(s - 1) * W];
+    };
+    float g[MAXS];                  // gamma of the row below; "row h": all mass on the last state
+    double sf[NV], m2[NV];
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s) g[s] = s == MAXS - 1 ? 1.f : 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) { sf[k] = 0.0; m2[k] = 0.0; }
+    auto back = [&](const Back& bk, const Row& rw, int y) {
+        float u[MAXS], rh[MAXS], gam[MAXS];
+        u[0] = 1.f;
+        rh[0] = 0.f;
+#pragma unroll
+        for (int s = 1; s < MAXS; ++s) {
+            const float v = bk.v[s - 1];
+            const bool is_u = __float_as_int(v) < 0;
+            u[s] = is_u ? -v : 1.f - v;
+            rh[s] = is_u ? 1.f + v : v;
+        }
+        float Q = g[MAXS - 1], tot;
+        gam[MAXS - 1] = u[MAXS - 1] * Q;
+        tot = gam[MAXS - 1];
+#pragma unroll
+        for (int s = MAXS - 2; s >= 0; --s) {
+            Q = fmaf(rh[s + 1], Q, g[s]);
+            gam[s] = u[s] * Q;
+            tot += gam[s];
+        }
+        const float inv = __builtin_amdgcn_rcpf(tot);      // tot = the mass of the row below, 1 up to rounding
+#pragma unroll
+        for (int s = 0; s < MAXS; ++s) g[s] = gam[s] * inv;
+        float acc = 0.f;
+        const double wy = (double)(2 * y + 1);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            acc += g[k];
+            const double G = (double)fminf(acc, 1.f);
+            sf[k] += G;
+            m2[k] = fma(G, wy, m2[k]);
+        }
+        if constexpr (POST) {
+            float E[MAXS], pl[MAXS], pf[NF ? NF : 1], t[MAXS], qs = 0.f;
+            marg_emissions<MAXS, KIND, NF>(rw, inv_tau, first_mask, S, n_free, E, pl, pf);
+#pragma unroll
+            for (int s = 0; s < MAXS; ++s) {
+                const float q = s < S ? g[s] * __builtin_amdgcn_rcpf(E[s]) : 0.f;       // E >= 2^-40 for a real state
+                qs += q;
+                t[s] = q * pl[s];
+            }
+            float* __restrict__ pp = post + (pix0 + (int64_t)y * W) * C;
+#pragma unroll
+            for (int s = 0; s < MAXS; ++s)
+                if ((first_mask >> s) & 1) {            // wave-uniform: the first state of a class collects the later ones and stores
+                    float v = t[s];
+#pragma unroll
+                    for (int s2 = s + 1; s2 < MAXS; ++s2)
+                        if (s2 < S && L.cls[s2] == L.cls[s]) v += t[s2];
+                    pp[L.cls[s]] = v;
+                }
+            if constexpr (NF > 0) {
+#pragma unroll
+                for (int j = 0; j < NF; ++j)
+                    if (j < n_free) pp[L.fcls[j]] = pf[j] * qs;
+            }
+        }
+    };
+    {
+        Back va[R], vb[R];
+        Row za[POST ? R : 1], zb[POST ? R : 1];
+        auto load_batch = [&](Back (&bk)[R], Row (&rw)[POST ? R : 1], int y1) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                load_back(bk[r], y1 - r);
+                if constexpr (POST) load_row(rw[r], y1 - r);
+            }
+        };
+        auto run_batch = [&](const Back (&bk)[R], const Row (&rw)[POST ? R : 1], int y1) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) back(bk[r], rw[POST ? r : 0], y1 - r);
+        };
+        int y1 = h_valid - 1;
+        load_batch(va, za, y1);
+        for (; y1 - 2 * R + 1 >= 0; y1 -= 2 * R) {
+            load_batch(vb, zb, y1 - R);
+            run_batch(va, za, y1);
+            load_batch(va, za, y1 - 2 * R);
+            run_batch(vb, zb, y1 - R);
+        }
+        if (y1 - R + 1 >= 0) {
+            load_batch(vb, zb, y1 - R);
+            run_batch(va, za, y1);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                va[r] = vb[r];
+                if constexpr (POST) za[r] = zb[r];
+            }
+            y1 -= R;
+        }
+#pragma unroll
+        for (int r = 0; r < R - 1; ++r)
+            if (y1 - r >= 0) back(va[r], za[POST ? r : 0], y1 - r);
+    }
+#pragma unroll
+    for (int k = 1; k < MAXS; ++k)
+        if (k < S) {
+            const double s1 = sf[k - 1], d = m2[k - 1] - s1 * s1;
+            surf[((int64_t)b * (S - 1) + k - 1) * W + x] = (float)s1;
+            var[((int64_t)b * (S - 1) + k - 1) * W + x] = (float)(d > 0.0 ? d : 0.0);
+        }
+    if constexpr (POST)
+        for (int y = h_valid; y < H; ++y)
+            for (int c = 0; c < C; ++c) post[(pix0 + (int64_t)y * W) * C + c] = 0.f;
+}
+
+struct MargCall {
+    const void* logits; int B, H, W, C; MargArgs L; int S, first_mask, n_free, h_valid, w_valid; float inv_tau; float *ws, *surf, *var, *logz, *post; hipStream_t st;
+};
+template <int MAXS, int KIND, int NF, bool POST>
+static void marg_launch(const MargCall& a) {
+    const dim3 grid((unsigned)((a.W + 63) / 64), 1, (unsigned)a.B), block(64);
+    hipLaunchKernelGGL((k_layout_marginals<MAXS, KIND, NF, POST>), grid, block, 0, a.st, a.logits, a.H, a.W, a.C, a.L, a.S, a.first_mask, a.n_free, a.h_valid, a.w_valid,
+                       a.inv_tau, a.ws, a.surf, a.var, a.logz, a.post);
+}
+template <int MAXS, int KIND, int NF>
+static void marg_post(const MargCall& a) {
+    if (a.post) marg_launch<MAXS, KIND, NF, true>(a);
+    else marg_launch<MAXS, KIND, NF, false>(a);
+}
+template <int MAXS>
+static void marg_kind(const MargCall& a, int kind) {
+    // free slots as in layout_decode.hip: 2 covers one or two lesion classes, 14 everything a layout can hold
+    if (kind == 0) {
+        if (a.n_free == 0) marg_post<MAXS, 0, 0>(a);
+        else if (a.n_free <= 2) marg_post<MAXS, 0, 2>(a);
+        else marg_post<MAXS, 0, 14>(a);
+    } else {
+        if (a.n_free == 0) marg_post<MAXS, 1, 0>(a);
+        else if (a.n_free <= 2) marg_post<MAXS, 1, 2>(a);
+        else marg_post<MAXS, 1, 14>(a);
+    }
+}
+
+extern "C" int64_t tcct_layout_marginals_ws_bytes(int B, int H, int W, int S, int n_free) {
+    if (B < 1 || H < 1 || W < 1 || S < 2 || S > 16 || n_free < 0 || n_free > 14) {
+        tcct_set_error("layout_marginals_ws_bytes: B=%d H=%d W=%d S=%d n_free=%d", B, H, W, S, n_free);
+        return -1;
+    }
+    return (int64_t)B * H * W * (marg_maxs(S) - 1) * (int64_t)sizeof(float);
+}
+
+extern "C" int tcct_layout_marginals(const void* logits, int kind, int B, int H, int W, int C, const int* layers, int S, int free_mask, int h_valid, int w_valid,
+                                     float tau, void* ws, float* surf, float* var, float* logz, float* post, tcct_stream_t stream) {
+    TCCT_CHECK(B >= 1 && H >= 1 && W >= 1, "layout_marginals: empty tensor");
+    TCCT_CHECK(B <= 65535, "layout_marginals: B=%d images in one call (at most 65535)", B);
+    TCCT_CHECK(C >= 2 && C <= 16, "layout_marginals: C=%d unsupported (2..16)", C);
+    TCCT_CHECK(kind == 0 || kind == 1, "layout_marginals: kind=%d (0 fp32 logits, 1 bf16 logits; a class map has no marginals)", kind);
+    TCCT_CHECK(S >= 2 && S <= 16 && layers, "layout_marginals: S=%d states (2..16)", S);
+    TCCT_CHECK(free_mask >= 0 && free_mask < (1 << C), "layout_marginals: free_mask=0x%x names a class outside 0..%d", free_mask, C - 1);
+    TCCT_CHECK(tau > 0.f && tau <= 3.0e38f, "layout_marginals: tau=%g (a positive temperature)", (double)tau);
+    int seen = free_mask, n_free = 0, first_mask = 0;
+    MargArgs L;
+    for (int s = 0; s < 16; ++s) {
+        const int c = layers[s < S ? s : S - 1];
+        if (s < S) {
+            TCCT_CHECK(c >= 0 && c < C, "layout_marginals: layers[%d]=%d outside 0..%d", s, c, C - 1);
+            TCCT_CHECK(s == 0 || c != layers[s - 1], "layout_marginals: layers[%d] repeats its neighbour (class %d)", s, c);
+            TCCT_CHECK(!((free_mask >> c) & 1), "layout_marginals: class %d is a layer and free", c);
+            if (!((seen >> c) & 1)) first_mask |= 1 << s;
+            seen |= 1 << c;
+        }
+        L.cls[s] = c;
+    }
+    TCCT_CHECK(seen == (1 << C) - 1, "layout_marginals: a class of 0..%d is neither a layer nor free", C - 1);
+    for (int c = 0; c < C; ++c)
+        if ((free_mask >> c) & 1) L.fcls[n_free++] = c;
+    for (int j = n_free; j < 14; ++j) L.fcls[j] = n_free ? L.fcls[n_free - 1] : 0;
+    TCCT_CHECK(h_valid >= 0 && h_valid <= H && w_valid >= 0 && w_valid <= W, "layout_marginals: valid region %dx%d outside 0..%d x 0..%d", h_valid, w_valid, H, W);
+    TCCT_CHECK(h_valid <= 4096, "layout_marginals: h_valid=%d rows (at most 4096, as layout_decode)", h_valid);
+    TCCT_CHECK((int64_t)W + 63 < (1LL << 31), "layout_marginals: W=%d too large", W);
+    TCCT_CHECK((int64_t)H * W * C * 4 < (1LL << 31), "layout_marginals: H*W*C = %lld values per image (the pixel offsets are 32 bits)", (long long)H * W * C);
+    TCCT_CHECK(logits && ws && surf && var && logz, "layout_marginals: logits, ws, surf, var and logz are required");
+    hipStream_t st = (hipStream_t)stream;
+    if (h_valid == 0 || w_valid == 0) {         // an empty valid region launches nothing and zeroes every output
+        hipError_t e = hipMemsetAsync(surf, 0, sizeof(float) * (size_t)B * (S - 1) * W, st);
+        if (e == hipSuccess) e = hipMemsetAsync(var, 0, sizeof(float) * (size_t)B * (S - 1) * W, st);
+        if (e == hipSuccess) e = hipMemsetAsync(logz, 0, sizeof(float) * (size_t)B * W, st);
+        if (e == hipSuccess && post) e = hipMemsetAsync(post, 0, sizeof(float) * (size_t)B * H * W * C, st);
+        if (e != hipSuccess) { tcct_set_error("layout_marginals: memset failed"); return -2; }
+        return 0;
+    }
+    const MargCall a = {logits, B, H, W, C, L, S, first_mask, n_free, h_valid, w_valid, 1.f / tau, (float*)ws, surf, var, logz, post, st};
+    // per-state register arrays and loops are sized by MAXS
+    const int maxs = marg_maxs(S);
+    if (maxs == 5) marg_kind<5>(a, kind);
+    else if (maxs == 6) marg_kind<6>(a, kind);
+    else if (maxs == 10) marg_kind<10>(a, kind);
+    else marg_kind<16>(a, kind);
+    TCCT_LAUNCH_OK();
+}
+
+// ----------------------------------------------------------------------- per-image soft scores: the expected surfaces against the label's integer ones
+#define MSB 256
+// fixed order: every thread's strided partial, then a binary tree over the block
+__device__ __forceinline__ double marg_block_sum(double v, double* sm /* MSB */) {
+    __syncthreads();
+    sm[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = MSB / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
+        __syncthreads();
+    }
+    return sm[0];
+}
+// one block per image; table row = [sum |surf - bnd_lab| per surface | sum (surf - bnd_lab)^2 per surface | sum var per surface | n_col]
+__global__ void __launch_bounds__(MSB) k_eval_soft_scores(const float* __restrict__ surf, const float* __restrict__ var, const int32_t* __restrict__ bnd_lab, int S, int W,
+                                                          int h_valid, int w_valid, double* __restrict__ table) {
+    __shared__ double sm[MSB];
+    const int b = blockIdx.x, NS = S - 1;
+    double* row = table + (int64_t)b * (3 * NS + 1);
+    const float* sp = surf + (int64_t)b * NS * W;
+    const float* vp = var + (int64_t)b * NS * W;
+    const int32_t* bl = bnd_lab + (int64_t)b * NS * W;
+    // a column is annotated when it lies in the valid region and its label leaves state 0 somewhere (6b)
+    double ncol = 0.0;
+    for (int x = threadIdx.x; x < w_valid; x += MSB) ncol += bl[x] < h_valid ? 1.0 : 0.0;
+    ncol = marg_block_sum(ncol, sm);
+    if (threadIdx.x == 0) row[3 * NS] = ncol;
+    for (int k = 0; k < NS; ++k) {
+        double sa = 0.0, sq = 0.0, sv = 0.0;
+        for (int x = threadIdx.x; x < w_valid; x += MSB)
+            if (bl[x] < h_valid) {
+                const double d = (double)sp[(int64_t)k * W + x] - (double)bl[(int64_t)k * W + x];
+                sa += fabs(d);
+                sq += d * d;
+                sv += (double)vp[(int64_t)k * W + x];
+            }
+        sa = marg_block_sum(sa, sm);
+        sq = marg_block_sum(sq, sm);
+        sv = marg_block_sum(sv, sm);
+        if (threadIdx.x == 0) { row[k] = sa; row[NS + k] = sq; row[2 * NS + k] = sv; }
+    }
+}
+extern "C" int tcct_eval_soft_scores(const float* surf, const float* var, const int32_t* bnd_lab, int B, int S, int W, int h_valid, int w_valid, double* table,
+                                     tcct_stream_t stream) {
+    TCCT_CHECK(B >= 1 && W >= 1, "eval_soft_scores: empty tensor");
+    TCCT_CHECK(S >= 2 && S <= 16, "eval_soft_scores: S=%d states unsupported (2..16)", S);
+    TCCT_CHECK(h_valid >= 1 && w_valid >= 1 && w_valid <= W, "eval_soft_scores: valid region %dx%d (W = %d)", h_valid, w_valid, W);
+    TCCT_CHECK(surf && var && bnd_lab && table, "eval_soft_scores: surf, var, bnd_lab and table are required");
+    hipLaunchKernelGGL(k_eval_soft_scores, dim3((unsigned)B), dim3(MSB), 0, (hipStream_t)stream, surf, var, bnd_lab, S, W, h_valid, w_valid, table);
+    TCCT_LAUNCH_OK();
+}

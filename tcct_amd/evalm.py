@@ -14,7 +14,11 @@ boundary rows are layer positions by construction.  `Evaluator.add(..., decode='
 
 `Layout` / `layout_decode` (tcct_amd/csrc/layout_decode.hip) carry the same decode over a layout: a top-to-bottom sequence of states whose classes
 may repeat (background above and below the retina) plus free classes (lesions) that may sit anywhere.  `Evaluator(..., layout=...)` decodes prediction AND
-label through it and scores the surfaces between the states (`tcct_eval_layout_scores`)."""
+label through it and scores the surfaces between the states (`tcct_eval_layout_scores`).
+
+`layout_marginals` (tcct_amd/csrc/layout_marginals.hip) is the sum-product counterpart of `layout_decode`: the expected row of every surface over
+ALL ordered state sequences (sub-pixel), its variance as a per-column confidence, the column log-partition and, on request, the per-pixel class posterior.
+`Evaluator(..., soft=True)` scores those surfaces against the label's next to the hard decode (`tcct_eval_soft_scores`)."""
 import ctypes
 
 import numpy as np
@@ -181,6 +185,84 @@ def layout_decode(pred, layout, valid=None, want_best=False, want_state=False):
     return mask, bnd, changed, best, state
 
 
+def layout_marginals(logits, layout, valid=None, tau=1.0, want_post=False):
+    """Layout marginals (layout_marginals.hip): per image and valid column the posterior over ALL non-decreasing state sequences of `layout`, a sequence
+    weighing prod_y E(y, s(y)) with E(y,s) = p~(y, layers[s]) + sum over the free classes of p~(y,f), p~ = max(softmax_c(clamp(logit, -1024, 1024) / tau), 2^-40).
+    logits: fp32 / bf16 NHWC [B,H,W,C] (a uint8 class map has no marginals); valid = (h_valid, w_valid), default the whole image, h_valid <= 4096; tau > 0.
+    -> (surf fp32 [B,S-1,W], the expected row at which state k starts: the expectation of `layout_decode`'s bnd, non-decreasing in k; var fp32 [B,S-1,W], its
+    variance in px^2; logz fp32 [B,W], the column log-partition; post fp32 [B,H,W,C] | None, the per-pixel class posterior, sums to 1 over C in the valid
+    region).  Everything outside the valid region reads 0.  Allocates its workspace, no sync; two calls give the same bits."""
+    if not isinstance(layout, Layout):
+        raise TcctError(f'layout_marginals: layout must be an evalm.Layout, got {type(layout).__name__}')
+    try:
+        tau = float(tau)
+    except (TypeError, ValueError):
+        raise TcctError(f'layout_marginals: tau={tau!r} (a positive temperature)')
+    if not 0.0 < tau < float('inf'):
+        raise TcctError(f'layout_marginals: tau={tau!r} (a positive temperature)')
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        raise TcctError('layout_marginals: logits must be a CUDA tensor (no CPU fallback)')
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TcctError(f'layout_marginals: fp32 / bf16 logits [B,H,W,C] expected, got {logits.dtype} (a class map has no marginals)')
+    C, S = layout.n_class, layout.n_states
+    if logits.dim() != 4 or logits.shape[3] != C:
+        raise TcctError(f'layout_marginals: logits {tuple(logits.shape)} are not NHWC [B,H,W,{C}]')
+    B, H, W = logits.shape[:3]
+    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    dev = logits.device
+    nbytes = lib.layout_marginals_ws_bytes(B, H, W, S, len(layout.free))
+    if nbytes < 0:
+        raise TcctError(f'tcct_layout_marginals_ws_bytes failed: {lib.last_error()}')
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    sv = torch.empty((2, B, S - 1, W), device=dev, dtype=torch.float32)
+    logz = torch.empty((B, W), device=dev, dtype=torch.float32)
+    post = torch.empty((B, H, W, C), device=dev, dtype=torch.float32) if want_post else None
+    lib.layout_marginals(logits.contiguous(), _KIND[logits.dtype], B, H, W, C, layout._c_layers, S, layout.free_mask, hv, wv, tau, ws, sv[0], sv[1], logz, post)
+    return sv[0], sv[1], logz, post
+
+
+def soft_table_width(layout):
+    return 3 * (layout.n_states - 1) + 1
+
+
+def eval_soft_scores(surf, var, bnd_lab, valid, table=None, row=0):
+    """surf, var fp32 [B,S-1,W] as `layout_marginals` returns them, bnd_lab int32 [B,S-1,W] the label's surfaces (`layout_decode` of the label)
+    -> fp64 [B, 3(S-1) + 1] = sum |surf - bnd_lab| | sum (surf - bnd_lab)^2 | sum var per surface, then n_col, over the annotated columns (include/tcct_hip.h).
+    `table`, `row` as `eval_scores`."""
+    ok = all(torch.is_tensor(t) and t.is_cuda and t.dim() == 3 for t in (surf, var, bnd_lab))
+    if not ok or surf.dtype != torch.float32 or var.dtype != torch.float32 or bnd_lab.dtype != torch.int32 or not (surf.shape == var.shape == bnd_lab.shape):
+        raise TcctError('eval_soft_scores: surf, var fp32 [B,S-1,W] and bnd_lab int32 [B,S-1,W] on the device expected')
+    B, NS, W = surf.shape
+    wid = 3 * NS + 1
+    if table is None:
+        table, row = torch.empty((B, wid), device=surf.device, dtype=torch.float64), 0
+    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == wid and table.is_contiguous()):
+        raise TcctError(f'eval_soft_scores: table must be a contiguous CUDA fp64 [N, {wid}]')
+    if row < 0 or row + B > table.shape[0]:
+        raise TcctError(f'eval_soft_scores: rows {row}..{row + B} do not fit a table of {table.shape[0]} images')
+    out = table[row:row + B]
+    lib.eval_soft_scores(surf.contiguous(), var.contiguous(), bnd_lab.contiguous(), B, NS + 1, W, int(valid[0]), int(valid[1]), out)
+    return out
+
+
+def aggregate_soft(table, n_states):
+    """per-image soft table (CPU tensor or numpy, [N, 3(S-1) + 1]) -> dict: `mad_soft`, `rmse_soft` [S-1] in pixels and `spread_rms` [S-1], the root of the mean
+    posterior variance, pooled over the annotated columns of all images (NaN when there is none), `soft_table`"""
+    nb = n_states - 1
+    t = np.asarray(table.detach().cpu().numpy() if torch.is_tensor(table) else table, dtype=np.float64).reshape(-1, 3 * nb + 1)
+    ncol = float(t[:, 3 * nb].sum())
+    if ncol > 0:
+        mad, rmse, spread = t[:, :nb].sum(0) / ncol, np.sqrt(t[:, nb:2 * nb].sum(0) / ncol), np.sqrt(t[:, 2 * nb:3 * nb].sum(0) / ncol)
+    else:
+        mad, rmse, spread = np.full(nb, np.nan), np.full(nb, np.nan), np.full(nb, np.nan)
+    return {'mad_soft': mad, 'rmse_soft': rmse, 'spread_rms': spread, 'soft_table': t}
+
+
+def per_image_soft_header(n_states):
+    return ([f'sum_abs_soft_{k}' for k in range(1, n_states)] + [f'sum_sq_soft_{k}' for k in range(1, n_states)] + [f'sum_var_{k}' for k in range(1, n_states)]
+            + ['n_col'])
+
+
 def eval_layout_scores(counts, bnd_pred, bnd_lab, layout, valid, table=None, row=0):
     """counts as `eval_counts` returns them (decoded mask against the label), bnd_pred / bnd_lab the surfaces `layout_decode` gives for prediction and label
     -> fp64 [B, 2C + 2(S-1) + 1] = Dice_c | IoU_c | sum |d| per surface | sum d^2 per surface | n_col (include/tcct_hip.h).  `table`, `row` as `eval_scores`."""
@@ -259,7 +341,7 @@ def read_mask_png(path, divide=30):
 
 def metrics_dict(res):
     """the dict of `aggregate` without the table, as plain Python numbers (what metrics.json holds)"""
-    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res.items() if k != 'table'}
+    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res.items() if k not in ('table', 'soft_table')}
 
 
 def per_image_header(n_class, layout=None):
@@ -272,9 +354,11 @@ def per_image_header(n_class, layout=None):
 class Evaluator:
     """Scores of up to `n_images` images in a preallocated device table.  `add` launches the two kernels (and the fill of their workspace) and never syncs;
     `result` makes ONE device -> host copy and aggregates on the host.  With a `layout` `add(..., decode='ordered')` runs prediction and label
-    through `layout_decode`, scores Dice / IoU of the decoded mask and the surface errors between the two decodes; the table then is `eval_layout_scores`'."""
+    through `layout_decode`, scores Dice / IoU of the decoded mask and the surface errors between the two decodes; the table then is `eval_layout_scores`'.
+    With `soft=True` `add(..., decode='ordered')` also runs `layout_marginals` on the prediction at temperature `tau` (under the layout, or under
+    `Layout.identity(n_class)` without one) and fills a second table (`eval_soft_scores`) against the same label surfaces; the hard numbers do not change."""
 
-    def __init__(self, n_images, n_class, device, layout=None):
+    def __init__(self, n_images, n_class, device, layout=None, soft=False, tau=1.0):
         if n_images < 1 or not 2 <= n_class <= 16:
             raise TcctError(f'Evaluator: n_images={n_images}, n_class={n_class} (2..16)')
         if layout is not None and (not isinstance(layout, Layout) or layout.n_class != n_class):
@@ -282,12 +366,20 @@ class Evaluator:
         self.n_class, self.capacity, self.n, self.layout = n_class, int(n_images), 0, layout
         self.table = torch.zeros((self.capacity, table_width(n_class, layout)), device=device, dtype=torch.float64)
         self.decode, self.changed = 'argmax', None
+        self.soft, self.tau, self.soft_table = bool(soft), float(tau), None
+        if self.soft:
+            if not 0.0 < self.tau < float('inf'):
+                raise TcctError(f'Evaluator: tau={tau!r} (a positive temperature)')
+            self.soft_layout = layout if layout is not None else Layout.identity(n_class)
+            self.soft_table = torch.zeros((self.capacity, soft_table_width(self.soft_layout)), device=device, dtype=torch.float64)
 
     def add(self, pred, lab, valid=None, want_mask=False, decode='argmax'):
         """one batch; -> the scored mask uint8 [B,H,W] (device) when `want_mask`, else None.  decode='argmax': the per-pixel first maximum of the logits;
         'ordered': the logits go through `ordered_decode` first and its mask is what is scored (and returned); all batches of one Evaluator decode alike"""
         check_decode(decode)
         check_layout_decode(self.layout, decode)
+        if self.soft and decode != 'ordered':
+            raise TcctError(f"Evaluator(soft=True) scores the marginals of the ordered column model; decode={decode!r} has none (pass decode='ordered')")
         B, H, W = lab.shape
         if self.n + B > self.capacity:
             raise TcctError(f'Evaluator: {self.n} + {B} images exceed the {self.capacity} it was made for')
@@ -318,6 +410,10 @@ class Evaluator:
             eval_layout_scores(counts, bp, bl, self.layout, valid, table=self.table, row=self.n)
         else:
             eval_scores(counts, bp, bl, valid, table=self.table, row=self.n)
+        if self.soft:
+            surf, var, _, _ = layout_marginals(pred, self.soft_layout, valid, self.tau)
+            eval_soft_scores(surf, var, bl, valid, table=self.soft_table, row=self.n)
+            self.last_soft = (surf, var)                    # of this batch, on the device (KiteSeg.evaluate writes them out)
         self.n += B
         return mask
 
@@ -328,4 +424,7 @@ class Evaluator:
             res['changed_pixels'] = int(self.changed.item()) if self.changed is not None else 0
         if self.layout is not None:
             res['layers'], res['free'] = list(self.layout.layers), list(self.layout.free)
+        if self.soft:
+            res.update(aggregate_soft(self.soft_table[:self.n].cpu(), self.soft_layout.n_states))
+            res['tau'] = self.tau
         return res

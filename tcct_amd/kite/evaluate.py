@@ -10,7 +10,9 @@ Takes the flags of kite/main.py that build the dataset and the network (--db --n
   --layers      with --decode=ordered: the classes of the column states from top to bottom, e.g. 0,1,2,3,4,5,6,7,8,0 for a set whose class 0 lies above AND
                 below the retina; --free=9 names classes that are no layer (fluid, lesions).  Prediction and label then go through evalm.layout_decode and
                 MAD / RMSE are listed per surface `class above|class below`.  Default: the layout the dataset file stores (pack_dataset.py
-                --layers / --free), else none"""
+                --layers / --free), else none
+  --soft        with --decode=ordered: also run evalm.layout_marginals at temperature --tau and report MAD / RMSE of the expected, sub-pixel
+                surfaces and the RMS posterior spread per surface; --out then also holds surfaces.npz and per_image_soft.csv"""
 import argparse
 import os
 
@@ -45,6 +47,9 @@ def build_parser():
     p.add_argument('--layers', type=class_ids, default=None, help='with --decode=ordered: classes of the column states from top to bottom, e.g. 0,1,2,3,4,5,6,7,8,0 '
                    '(class 0 above and below the retina; DESIGN 6d); default: the layout stored in the dataset file, else classes increase with depth')
     p.add_argument('--free', type=class_ids, default=None, help='with --layers: classes that are no layer (fluid, lesions), e.g. 9')
+    p.add_argument('--soft', type=str2bool, default=False, help='with --decode=ordered: also score the expected (sub-pixel) surfaces of evalm.layout_marginals '
+                   'and report their posterior spread (DESIGN 6e); --out then also receives surfaces.npz and per_image_soft.csv')
+    p.add_argument('--tau', type=float, default=1.0, help='with --soft: softmax temperature of the marginals')
     p.add_argument('--bug', type=str2bool, default=False, help='Debug Mode: ten batches')
     return p
 
@@ -61,6 +66,10 @@ def parse_args(argv=None):
         raise SystemExit('--free needs --layers')
     if args.layers is not None and args.decode != 'ordered':
         raise SystemExit('--layers describes the ordered decode: pass --decode=ordered')
+    if args.soft and args.decode != 'ordered':
+        raise SystemExit('--soft=true scores the marginals of the ordered column model: pass --decode=ordered')
+    if args.soft and not 0.0 < args.tau < float('inf'):
+        raise SystemExit(f'--tau={args.tau}: a positive temperature')
     return args
 
 
@@ -79,6 +88,9 @@ def report(res):
         lines.append(f"decode   {res['decode']}: {res['changed_pixels']} pixels differ from the per-pixel argmax")
     if 'layers' in res:
         lines.append(f"layout   layers {','.join(map(str, res['layers']))}" + (f", free {','.join(map(str, res['free']))}" if res['free'] else ''))
+    if 'mad_soft' in res:
+        lines.append('MAD soft ' + ' '.join(f'{v:7.3f}' for v in res['mad_soft']) + f"   {float(res['mad_soft'].mean()):.3f}   (expected surfaces, tau {res['tau']:g})")
+        lines.append('spread   ' + ' '.join(f'{v:7.3f}' for v in res['spread_rms']) + '   RMSE soft ' + ' '.join(f'{v:.3f}' for v in res['rmse_soft']))
     return '\n'.join(lines)
 
 
@@ -110,7 +122,8 @@ def main(argv=None):
     if args.layers is not None:
         from ..evalm import Layout
         layout = Layout(args.layers, args.free or (), dataset.out_channels)
-    res = keras.evaluate(split=args.split, bs=args.val_bs, out_dir=args.out or None, decode=args.decode, layout=layout)
+    soft = dict(soft=True, tau=args.tau) if args.soft else {}
+    res = keras.evaluate(split=args.split, bs=args.val_bs, out_dir=args.out or None, decode=args.decode, layout=layout, **soft)
     print(report(res))
     return res
 

@@ -94,6 +94,24 @@ class KiteSeg(KiteBack):
                 pred = MaskOneHot(idx, self.NB_CLASS)
         return pred
 
+    def predict_surfaces(self, img, layout=None, tau=1.0):
+        """Sub-pixel layer surfaces of a batch of images with their confidence (`evalm.layout_marginals`).  img [B,C,H,W] as the dataset stores it
+        (not padded: H and W are padded to multiples of 16 here and only the image itself is read back).  `layout`: an `evalm.Layout`; default the
+        dataset's, else classes increasing with depth.  -> (surf fp32 [B,S-1,W], the expected row at which state k starts; spread fp32 [B,S-1,W], its
+        standard deviation in px; logz fp32 [B,W], the column log-partition at temperature `tau`)."""
+        from .. import evalm
+        if layout is None:
+            layout = getattr(self.dataset, 'layout', None) or evalm.Layout.identity(self.NB_CLASS)
+        if not isinstance(layout, evalm.Layout):
+            raise TcctError(f'predict_surfaces: layout must be an evalm.Layout, got {type(layout).__name__}')
+        H, W = int(img.shape[-2]), int(img.shape[-1])
+        Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
+        if (Hp, Wp) != (H, W):
+            img = torch.nn.functional.pad(img, (0, Wp - W, 0, Hp - H))
+        lg = as_nhwc(self.predict(img, softmax=False))
+        surf, var, logz, _ = evalm.layout_marginals(lg, layout, (H, W), tau)
+        return surf[..., :W], var[..., :W].sqrt(), logz[..., :W]
+
     def fit(self, epochs=169):
         t0 = time.time()
         for i in range(self.epoch, epochs):
@@ -153,7 +171,7 @@ class KiteSeg(KiteBack):
             return ds.testSet(bs=bs)
         raise TcctError(f"evaluate(split={split!r}): this dataset has no evalSet(); only 'val' and 'test' are available")
 
-    def evaluate(self, split='val', bs=8, out_dir=None, flagDebug=False, decode='argmax', layout=None):
+    def evaluate(self, split='val', bs=8, out_dir=None, flagDebug=False, decode='argmax', layout=None, soft=False, tau=1.0):
         """Scores of a whole split in batches (tcct_amd/evalm.py): per-class Dice / IoU and per-boundary MAD / RMSE of the valid region (the image before
         `parse` padded it).  Eval mode, no gradients, main head only; the logits go straight to the counting kernel and nothing is read back before the end
         -- unless `out_dir` is given: then the mask of every batch is copied to the host and written as `{split}_{index:05d}.png` (gray = class x 30, cropped
@@ -162,7 +180,10 @@ class KiteSeg(KiteBack):
         mask is what is scored and written; the result and `metrics.json` then also carry `decode` and `changed_pixels` (pixels that differ from the argmax).
         `layout` (an `evalm.Layout`, with decode='ordered'; default: the dataset's `.layout`, if its file stores one): prediction and label go through
         `evalm.layout_decode` (background above and below, lesion classes), MAD / RMSE are those of the S-1 surfaces between the layout's states,
-        and the result also carries `layers` and `free`."""
+        and the result also carries `layers` and `free`.
+        `soft` (with decode='ordered'): the logits also go through `evalm.layout_marginals` at temperature `tau`; the result then carries
+        `mad_soft`, `rmse_soft`, `spread_rms` per surface and `tau`, and `out_dir` also receives `surfaces.npz` (per image `NAME.surf` and `NAME.spread`,
+        fp32 [S-1, W] of the valid region) and `per_image_soft.csv`.  Without `soft` nothing changes."""
         import os
         from .. import evalm
         evalm.check_decode(decode)
@@ -172,7 +193,10 @@ class KiteSeg(KiteBack):
         batches = self._eval_batches(split, bs)
         n_max = int(getattr(batches, 'n_images', len(batches) * bs))
         evalm.check_layout_decode(layout, decode)
-        ev = evalm.Evaluator(max(n_max, 1), self.NB_CLASS, self.device, layout=layout)
+        if soft and decode != 'ordered':
+            raise TcctError(f"evaluate(soft=True) scores the marginals of the ordered column model: pass decode='ordered', not {decode!r}")
+        ev = evalm.Evaluator(max(n_max, 1), self.NB_CLASS, self.device, layout=layout, soft=soft, tau=tau)
+        surfaces = {}
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
         prev = torch.is_grad_enabled()
@@ -190,6 +214,10 @@ class KiteSeg(KiteBack):
                     m = mask[:, :valid[0], :valid[1]].cpu().numpy()
                     for j in range(m.shape[0]):
                         evalm.write_mask_png(os.path.join(out_dir, f'{split}_{first + j:05d}.png'), m[j])
+                    if soft:
+                        sf, sp = (t[..., :valid[1]].cpu().numpy() for t in (ev.last_soft[0], ev.last_soft[1].sqrt()))
+                        for j in range(m.shape[0]):
+                            surfaces[f'{split}_{first + j:05d}.surf'], surfaces[f'{split}_{first + j:05d}.spread'] = sf[j], sp[j]
                 if (self.args.bug or flagDebug) and i > 8:
                     break
         finally:
@@ -202,6 +230,10 @@ class KiteSeg(KiteBack):
                 json.dump(evalm.metrics_dict(res), f, indent=1)
             np.savetxt(os.path.join(out_dir, 'per_image.csv'), res['table'], delimiter=',', header=','.join(evalm.per_image_header(self.NB_CLASS, layout)), comments='',
                        fmt='%.17g')
+            if soft:
+                np.savez(os.path.join(out_dir, 'surfaces.npz'), **surfaces)
+                np.savetxt(os.path.join(out_dir, 'per_image_soft.csv'), res['soft_table'], delimiter=',',
+                           header=','.join(evalm.per_image_soft_header(ev.soft_layout.n_states)), comments='', fmt='%.17g')
         return res
 
     def train_step(self, img, lab):
