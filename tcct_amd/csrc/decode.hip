@@ -3,7 +3,7 @@
 //   D_0(c) = q(0, c);   M_{y-1}(c) = max_{c' <= c} D_{y-1}(c');   take_y(c) = (c == 0 || D_{y-1}(c) > M_{y-1}(c - 1));   D_y(c) = q(y, c) + M_{y-1}(c)
 //   c(h_valid - 1) = the first maximum of D_{h_valid-1};   c(y - 1) = the highest set bit of take_y at a position <= c(y)
 // h_valid <= 4096 keeps |D| <= 4096 * 2^18 = 2^30 inside int32.
-#include "common.h"
+#include "column_dp.h"
 
 // A wave owns 64 adjacent columns of ONE image, a lane owns a column: the loads of a wave instruction cover the 64 * C contiguous values of a row (as
 // k_eval_counts).  The forward pass walks the rows with the loads of the next DFR rows in flight while the add / max chain of the current DFR rows runs, and
@@ -16,13 +16,6 @@ template <int MAXC> struct DecodeCfg {
 };
 template <int MAXC> struct DecodeTake { typedef uint8_t type; };
 template <> struct DecodeTake<16> { typedef uint16_t type; };
-
-// q of one logit.  A false comparison yields the lower clamp: NaN -> -1024.  rintf rounds half to even; s * 256 is exact in fp32.
-__device__ __forceinline__ int decode_quant(float s) {
-    float t = s > -1024.f ? s : -1024.f;
-    t = t < 1024.f ? t : 1024.f;
-    return (int)rintf(t * 256.f);
-}
 
 // R rows from row y0 of one column as fp32.  Every address is clamped into the valid rows and the C classes, so no load sits behind a branch.  A row past the
 // end re-reads the last one and is not used.  A class c >= C is a COPY of class C - 1, and stays one through the recurrence: D_y(c) = D_y(C - 1) for every y (by
@@ -37,13 +30,13 @@ __device__ __forceinline__ void decode_load_rows(const T* __restrict__ base, int
         for (int c = 0; c < MAXC; ++c) z[r][c] = ldf(p + min(c, C - 1));
     }
 }
-// q of one pixel and its first maximum
+// q of one pixel (column_quant) and its first maximum
 template <int MAXC>
 __device__ __forceinline__ int decode_scores(const float (&z)[MAXC], int (&q)[MAXC]) {
-    int am = 0, mx = q[0] = decode_quant(z[0]);
+    int am = 0, mx = q[0] = column_quant(z[0]);
 #pragma unroll
     for (int c = 1; c < MAXC; ++c) {
-        q[c] = decode_quant(z[c]);
+        q[c] = column_quant(z[c]);
         if (q[c] > mx) { mx = q[c]; am = c; }
     }
     return am;
@@ -169,9 +162,7 @@ extern "C" int tcct_ordered_decode(const void* logits, int kind, int B, int H, i
     TCCT_CHECK(B <= 65535, "ordered_decode: B=%d images in one call (at most 65535)", B);
     TCCT_CHECK(C >= 2 && C <= 16, "ordered_decode: C=%d unsupported (2..16)", C);
     TCCT_CHECK(kind == 0 || kind == 1, "ordered_decode: kind=%d (0 fp32 logits, 1 bf16 logits)", kind);
-    TCCT_CHECK(h_valid >= 0 && h_valid <= H && w_valid >= 0 && w_valid <= W, "ordered_decode: valid region %dx%d outside 0..%d x 0..%d", h_valid, w_valid, H, W);
-    TCCT_CHECK(h_valid <= 4096, "ordered_decode: h_valid=%d rows (at most 4096: the column sums are int32)", h_valid);
-    TCCT_CHECK((int64_t)W + 63 < (1LL << 31), "ordered_decode: W=%d too large", W);
+    if (column_check_limits("ordered_decode", ": the column sums are int32", H, W, 0 /* 64-bit row addresses */, h_valid, w_valid)) return -1;
     TCCT_CHECK(logits && take_ws && mask && bnd && changed, "ordered_decode: logits, take_ws, mask, bnd and changed are required");
     hipStream_t st = (hipStream_t)stream;
     // `changed` is the one output that is accumulated; an empty valid region launches nothing and zeroes all of them

@@ -1,7 +1,7 @@
 // Evaluation of a batch of predictions against class-index labels: per-image class counts {I, P, G}, layer-boundary rows of prediction and
 // label (the counting definition of k_mask_boundaries, loss.hip) and the argmax mask in ONE pass over the logits, then the per-image score
 // table.  Every accumulated quantity is an integer: the atomics are order-independent and every number is reproducible bit for bit.
-#include "common.h"
+#include "column_dp.h"        // block_tree_sum
 
 // A block owns 64 adjacent columns x ERCH rows of ONE image: ESEG waves, wave s takes the rows r with r % ESEG == s, so that at any time the
 // block's waves read adjacent rows.  A lane owns a column: the loads of a wave instruction cover the 64 * C contiguous values of a row.
@@ -153,22 +153,13 @@ extern "C" int tcct_eval_counts(const void* pred, int pred_kind, const uint8_t* 
 
 // ----------------------------------------------------------------------- per-image score table from the integer counts
 #define ESB 256
-__device__ __forceinline__ long long eval_block_sum(long long v, long long* sm /* ESB */) {
-    __syncthreads();
-    sm[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = ESB / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sm[0];
-}
-// one block per image; table row = [Dice_c | IoU_c | sum |d| per boundary | sum d^2 per boundary | n_col], sums over the annotated columns
+// one block per image; table row = [Dice_c | IoU_c | sum |d| per boundary | sum d^2 per boundary | n_col], sums over the annotated columns.  The boundaries
+// are the S - 1 surfaces between the S states of a layout (tcct_eval_layout_scores) or, with S = C, the C - 1 between the classes (tcct_eval_scores)
 __global__ void __launch_bounds__(ESB) k_eval_scores(const int32_t* __restrict__ counts, const int32_t* __restrict__ bnd_pred, const int32_t* __restrict__ bnd_lab, int C,
-                                                     int W, int h_valid, int w_valid, double* __restrict__ table) {
+                                                     int S, int W, int h_valid, int w_valid, double* __restrict__ table) {
     __shared__ long long sm[ESB];
-    const int b = blockIdx.x;
-    double* row = table + (int64_t)b * (4 * C - 1);
+    const int b = blockIdx.x, NS = S - 1;
+    double* row = table + (int64_t)b * (2 * C + 2 * NS + 1);
     if ((int)threadIdx.x < C) {
         const int32_t* q = counts + ((int64_t)b * C + threadIdx.x) * 3;
         const long long I = q[0], P = q[1], G = q[2];
@@ -176,17 +167,17 @@ __global__ void __launch_bounds__(ESB) k_eval_scores(const int32_t* __restrict__
         row[C + threadIdx.x] = (double)(I + 1) / (double)(P + G - I + 1);
     }
     if (!bnd_pred) {        // no boundary tables: the boundary columns and n_col read 0 (aggregate() then reports NaN distances)
-        for (int j = threadIdx.x; j < 2 * C - 1; j += ESB) row[2 * C + j] = 0.0;
+        for (int j = threadIdx.x; j < 2 * NS + 1; j += ESB) row[2 * C + j] = 0.0;
         return;
     }
-    const int32_t* bp = bnd_pred + (int64_t)b * (C - 1) * W;
-    const int32_t* bl = bnd_lab + (int64_t)b * (C - 1) * W;
-    // a column is annotated when it lies in the valid region and its label holds at least one pixel of a class >= 1
+    const int32_t* bp = bnd_pred + (int64_t)b * NS * W;
+    const int32_t* bl = bnd_lab + (int64_t)b * NS * W;
+    // a column is annotated when it lies in the valid region and its label leaves state 0 (holds a pixel of a class >= 1) somewhere
     long long ncol = 0;
     for (int x = threadIdx.x; x < w_valid; x += ESB) ncol += bl[x] < h_valid;
-    ncol = eval_block_sum(ncol, sm);
-    if (threadIdx.x == 0) row[4 * C - 2] = (double)ncol;
-    for (int k = 0; k < C - 1; ++k) {
+    ncol = block_tree_sum<long long, ESB>(ncol, sm);
+    if (threadIdx.x == 0) row[2 * C + 2 * NS] = (double)ncol;
+    for (int k = 0; k < NS; ++k) {
         long long sa = 0, sq = 0;
         for (int x = threadIdx.x; x < w_valid; x += ESB)
             if (bl[x] < h_valid) {
@@ -194,9 +185,9 @@ __global__ void __launch_bounds__(ESB) k_eval_scores(const int32_t* __restrict__
                 sa += d < 0 ? -d : d;
                 sq += d * d;
             }
-        sa = eval_block_sum(sa, sm);
-        sq = eval_block_sum(sq, sm);
-        if (threadIdx.x == 0) { row[2 * C + k] = (double)sa; row[3 * C - 1 + k] = (double)sq; }
+        sa = block_tree_sum<long long, ESB>(sa, sm);
+        sq = block_tree_sum<long long, ESB>(sq, sm);
+        if (threadIdx.x == 0) { row[2 * C + k] = (double)sa; row[2 * C + NS + k] = (double)sq; }
     }
 }
 extern "C" int tcct_eval_scores(const int32_t* counts, const int32_t* bnd_pred, const int32_t* bnd_lab, int B, int C, int W, int h_valid, int w_valid, double* table,
@@ -206,6 +197,15 @@ extern "C" int tcct_eval_scores(const int32_t* counts, const int32_t* bnd_pred, 
     TCCT_CHECK(h_valid >= 1 && w_valid >= 1 && w_valid <= W, "eval_scores: valid region %dx%d (W = %d)", h_valid, w_valid, W);
     TCCT_CHECK(counts && table, "eval_scores: counts and table are required");
     TCCT_CHECK((bnd_pred == nullptr) == (bnd_lab == nullptr), "eval_scores: bnd_pred and bnd_lab come together (or both NULL)");
-    hipLaunchKernelGGL(k_eval_scores, dim3((unsigned)B), dim3(ESB), 0, (hipStream_t)stream, counts, bnd_pred, bnd_lab, C, W, h_valid, w_valid, table);
+    hipLaunchKernelGGL(k_eval_scores, dim3((unsigned)B), dim3(ESB), 0, (hipStream_t)stream, counts, bnd_pred, bnd_lab, C, C, W, h_valid, w_valid, table);
+    TCCT_LAUNCH_OK();
+}
+extern "C" int tcct_eval_layout_scores(const int32_t* counts, const int32_t* bnd_pred, const int32_t* bnd_lab, int B, int C, int S, int W, int h_valid, int w_valid,
+                                       double* table, tcct_stream_t stream) {
+    TCCT_CHECK(B >= 1 && W >= 1, "eval_layout_scores: empty tensor");
+    TCCT_CHECK(C >= 2 && C <= 16 && S >= 2 && S <= 16, "eval_layout_scores: C=%d classes, S=%d states unsupported (2..16 each)", C, S);
+    TCCT_CHECK(h_valid >= 1 && w_valid >= 1 && w_valid <= W, "eval_layout_scores: valid region %dx%d (W = %d)", h_valid, w_valid, W);
+    TCCT_CHECK(counts && bnd_pred && bnd_lab && table, "eval_layout_scores: counts, bnd_pred, bnd_lab and table are required");
+    hipLaunchKernelGGL(k_eval_scores, dim3((unsigned)B), dim3(ESB), 0, (hipStream_t)stream, counts, bnd_pred, bnd_lab, C, S, W, h_valid, w_valid, table);
     TCCT_LAUNCH_OK();
 }

@@ -1,17 +1,14 @@
 // Layout decode: the column dynamic programme of decode.hip over a LAYOUT -- a top-to-bottom sequence of S states, each with a class (classes may
-// repeat: 0,1,..,C-1,0 is "background on both sides"), plus free classes (lesions) that any state may show.  With q as in decode.hip (decode_quant; a uint8
+// repeat: 0,1,..,C-1,0 is "background on both sides"), plus free classes (lesions) that any state may show.  With q as in decode.hip (column_quant; a uint8
 // class map scores 256 on its class, 0 elsewhere), F(y) = the first maximum of q(y, f) over the free classes in ascending order and f*(y) its class:
 //   e(y, s) = max(q(y, layers[s]), F(y));   state s shows layers[s] when q(y, layers[s]) >= F(y), else f*(y)
 //   D_{-1} = 0;   M_{y-1}(s) = max_{s' <= s} D_{y-1}(s');   take_y(s) = (s == 0 || D_{y-1}(s) > M_{y-1}(s - 1));   D_y(s) = e(y, s) + M_{y-1}(s)
 //   s(h_valid - 1) = the first maximum of D_{h_valid-1};   s(y - 1) = the highest set bit of take_y at a position <= s(y)
 // h_valid <= 4096 keeps |D| <= 2^30 inside int32.  layers = 0..C-1 without free classes is tcct_ordered_decode, bit for bit.
-#include "common.h"
-#include <type_traits>
+#include "column_dp.h"
 
-// The schedule is k_ordered_decode's: a wave owns 64 adjacent columns of ONE image, a lane owns a column; the forward pass walks down with the loads of the
-// next LFR rows in flight under the add / max chain of the current ones, the backward pass of the same wave walks up with LBR rows in flight.  What differs:
-//  * the layout is wave-uniform and lives in scalar registers (LayoutArgs is a kernel argument).  State s loads ITS value from `image + layers[s]`, a uniform
-//    base, plus the pixel's 32-bit offset: no register array is indexed at run time, and a repeated class reads the line its first use brought in.
+// Layout contract and schedule: column_dp.h.  The forward pass walks down with the loads of the next LFR rows in flight under the add / max chain of the
+// current ones, the backward pass of the same wave walks up with LBR rows in flight.  What is this kernel's own:
 //  * the first argmax over all C classes (smallest class on ties) cannot be taken in load order.  It is the maximum of the keys (q << 4) + (15 - class): q fits
 //    19 bits plus sign, so the key orders by q first and by the smaller class second.  The same key over the free classes gives F = key >> 4 and f*.
 //  * per pixel the forward pass leaves one word in the workspace: the take bits in [0, TB), with free classes the "this state shows f*" bits in [TB, 2 TB)
@@ -19,7 +16,6 @@
 //  * states >= S are COPIES of state S - 1 (the same class, so the same e and by induction the same D): under the strict comparisons a copy never sets a take
 //    bit and never is a first maximum, so no loop asks `s < S`.  Free slots >= n_free are copies of the last free class and never win either.
 #define LBR 16
-struct LayoutArgs { int cls[16]; int fcls[14]; };
 template <int MAXS> struct LayoutCfg {
     static constexpr int LFR = MAXS <= 8 ? 8 : 4;       // forward rows per batch
     static constexpr int TB = MAXS <= 8 ? 8 : 16;       // take bits per word
@@ -28,17 +24,7 @@ template <int BYTES> struct LayoutWord;
 template <> struct LayoutWord<1> { typedef uint8_t type; };
 template <> struct LayoutWord<2> { typedef uint16_t type; };
 template <> struct LayoutWord<4> { typedef uint32_t type; };
-// 5 = a 5-class set as it is, 6 = with the wrap, 10 = a 9-class set with the wrap.  The kernel runs at the length of its add / max chain, so a padded state costs
-// what a real one does: 6 states take 1.18 x the time of 5 (profiles/layout_decode_summary.md)
-static inline int layout_maxs(int S) { return S <= 5 ? 5 : (S <= 6 ? 6 : (S <= 10 ? 10 : 16)); }
-static inline int layout_word_bytes(int S, int n_free) { return (layout_maxs(S) <= 8 ? 1 : 2) * (n_free ? 2 : 1); }
-
-// decode.hip's decode_quant: a false comparison yields the lower clamp (NaN -> -1024); rintf rounds half to even; s * 256 is exact in fp32
-__device__ __forceinline__ int layout_quant(float s) {
-    float t = s > -1024.f ? s : -1024.f;
-    t = t < 1024.f ? t : 1024.f;
-    return (int)rintf(t * 256.f);
-}
+static inline int layout_word_bytes(int S, int n_free) { return (column_maxs(S) <= 8 ? 1 : 2) * (n_free ? 2 : 1); }
 
 template <int MAXS, int KIND, int NF> struct LayoutRow {
     float z[KIND == 2 ? 1 : MAXS];          // the logit of every state's class
@@ -48,7 +34,7 @@ template <int MAXS, int KIND, int NF> struct LayoutRow {
 
 // KIND: 0 fp32 logits, 1 bf16 logits, 2 uint8 class map.  NF: free-class slots (0: the layout has none; KIND 2 only asks NF > 0)
 template <int MAXS, int KIND, int NF>
-__global__ void __launch_bounds__(64) k_layout_decode(const void* __restrict__ pred, int H, int W, int C, const LayoutArgs L, int S, int free_mask, int h_valid,
+__global__ void __launch_bounds__(64) k_layout_decode(const void* __restrict__ pred, int H, int W, int C, const ColumnLayout L, int S, int free_mask, int h_valid,
                                                       int w_valid, void* __restrict__ ws_, uint8_t* mask, int32_t* __restrict__ bnd, int32_t* __restrict__ changed,
                                                       int32_t* __restrict__ best, uint8_t* __restrict__ state) {
     constexpr bool FREE = NF > 0;
@@ -64,22 +50,20 @@ __global__ void __launch_bounds__(64) k_layout_decode(const void* __restrict__ p
     int n_changed = 0;
     if (col_valid) {
         // ---------------------------------------------------------------- forward: D, take / free words, first argmax of q and f*
-        // image base (uniform) + class (uniform) + pixel offset (32 bits per lane: H * W * C * 4 < 2^31 is checked by the caller).  Every row address is
-        // clamped into the valid rows, so no load sits behind a branch; a row past the end re-reads the last one and is not used.
         const int esz = KIND == 2 ? 1 : (int)sizeof(T) * C;
         const char* img = (const char*)pred + (int64_t)b * H * W * esz;
         const uint32_t col_off = (uint32_t)x * (uint32_t)esz, rsb = (uint32_t)W * (uint32_t)esz;
         auto load_rows = [&](Row (&rw)[R], int y0) {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const uint32_t off = (uint32_t)min(y0 + r, h_valid - 1) * rsb + col_off;
+                const uint32_t off = column_row_offset(y0 + r, h_valid, rsb, col_off);
                 if constexpr (KIND == 2) rw[r].p = (int)*(const uint8_t*)(img + off);
                 else {
 #pragma unroll
-                    for (int s = 0; s < MAXS; ++s) rw[r].z[s] = ldf((const T*)((const char*)((const T*)img + L.cls[s]) + off));
+                    for (int s = 0; s < MAXS; ++s) rw[r].z[s] = ldf(column_at<T>(img, L.cls[s], off));
                     if constexpr (FREE) {
 #pragma unroll
-                        for (int j = 0; j < NF; ++j) rw[r].zf[j] = ldf((const T*)((const char*)((const T*)img + L.fcls[j]) + off));
+                        for (int j = 0; j < NF; ++j) rw[r].zf[j] = ldf(column_at<T>(img, L.fcls[j], off));
                     }
                 }
             }
@@ -105,7 +89,7 @@ __global__ void __launch_bounds__(64) k_layout_decode(const void* __restrict__ p
                 int key = 0;
 #pragma unroll
                 for (int s = 0; s < MAXS; ++s) {
-                    q[s] = layout_quant(rw.z[s]);
+                    q[s] = column_quant(rw.z[s]);
                     const int k = (int)(((uint32_t)q[s] << 4) + (uint32_t)kc[s]);         // one shift-add: kc is uniform
                     key = s == 0 ? k : max(key, k);
                 }
@@ -113,7 +97,7 @@ __global__ void __launch_bounds__(64) k_layout_decode(const void* __restrict__ p
                     int fk = 0;
 #pragma unroll
                     for (int j = 0; j < NF; ++j) {
-                        const int k = (int)(((uint32_t)layout_quant(rw.zf[j]) << 4) + (uint32_t)kf[j]);
+                        const int k = (int)(((uint32_t)column_quant(rw.zf[j]) << 4) + (uint32_t)kf[j]);
                         fk = j == 0 ? k : max(fk, k);
                     }
                     F = fk >> 4;                // arithmetic: floor(key / 16) = q
@@ -242,38 +226,8 @@ __global__ void __launch_bounds__(64) k_layout_decode(const void* __restrict__ p
     if (lane == 0 && n_changed) atomicAdd(changed + b, n_changed);
 }
 
-struct LayoutCall {
-    const void* pred; int B, H, W, C; LayoutArgs L; int S, free_mask, h_valid, w_valid; void* ws; uint8_t* mask; int32_t* bnd; int32_t* changed; int32_t* best;
-    uint8_t* state; hipStream_t st;
-};
-template <int MAXS, int KIND, int NF>
-static void layout_decode_launch(const LayoutCall& a) {
-    const dim3 grid((unsigned)((a.W + 63) / 64), 1, (unsigned)a.B), block(64);
-    hipLaunchKernelGGL((k_layout_decode<MAXS, KIND, NF>), grid, block, 0, a.st, a.pred, a.H, a.W, a.C, a.L, a.S, a.free_mask, a.h_valid, a.w_valid, a.ws, a.mask, a.bnd,
-                       a.changed, a.best, a.state);
-}
-template <int MAXS>
-static void layout_decode_kind(const LayoutCall& a, int kind, int n_free) {
-    // free slots: 2 covers one or two lesion classes, 14 everything a layout can hold; a class map only asks whether there is one
-    if (kind == 2) {
-        if (n_free == 0) layout_decode_launch<MAXS, 2, 0>(a);
-        else layout_decode_launch<MAXS, 2, 2>(a);
-    } else if (kind == 0) {
-        if (n_free == 0) layout_decode_launch<MAXS, 0, 0>(a);
-        else if (n_free <= 2) layout_decode_launch<MAXS, 0, 2>(a);
-        else layout_decode_launch<MAXS, 0, 14>(a);
-    } else {
-        if (n_free == 0) layout_decode_launch<MAXS, 1, 0>(a);
-        else if (n_free <= 2) layout_decode_launch<MAXS, 1, 2>(a);
-        else layout_decode_launch<MAXS, 1, 14>(a);
-    }
-}
-
 extern "C" int64_t tcct_layout_decode_ws_bytes(int B, int H, int W, int S, int n_free) {
-    if (B < 1 || H < 1 || W < 1 || S < 2 || S > 16 || n_free < 0 || n_free > 14) {
-        tcct_set_error("layout_decode_ws_bytes: B=%d H=%d W=%d S=%d n_free=%d", B, H, W, S, n_free);
-        return -1;
-    }
+    if (!column_ws_args_ok("layout_decode_ws_bytes", B, H, W, S, n_free)) return -1;
     return (int64_t)B * H * W * layout_word_bytes(S, n_free);
 }
 
@@ -285,26 +239,10 @@ extern "C" int tcct_layout_decode(const void* pred, int kind, int B, int H, int 
     TCCT_CHECK(kind >= 0 && kind <= 2, "layout_decode: kind=%d (0 fp32 logits, 1 bf16 logits, 2 uint8 classes)", kind);
     TCCT_CHECK(S >= 2 && S <= 16 && layers, "layout_decode: S=%d states (2..16)", S);
     TCCT_CHECK(free_mask >= 0 && free_mask < (1 << C), "layout_decode: free_mask=0x%x names a class outside 0..%d", free_mask, C - 1);
-    int seen = free_mask, n_free = 0;
-    LayoutArgs L;
-    for (int s = 0; s < 16; ++s) {
-        const int c = layers[s < S ? s : S - 1];
-        if (s < S) {
-            TCCT_CHECK(c >= 0 && c < C, "layout_decode: layers[%d]=%d outside 0..%d", s, c, C - 1);
-            TCCT_CHECK(s == 0 || c != layers[s - 1], "layout_decode: layers[%d] repeats its neighbour (class %d)", s, c);
-            TCCT_CHECK(!((free_mask >> c) & 1), "layout_decode: class %d is a layer and free", c);
-            seen |= 1 << c;
-        }
-        L.cls[s] = c;
-    }
-    TCCT_CHECK(seen == (1 << C) - 1, "layout_decode: a class of 0..%d is neither a layer nor free", C - 1);
-    for (int c = 0; c < C; ++c)
-        if ((free_mask >> c) & 1) L.fcls[n_free++] = c;
-    for (int j = n_free; j < 14; ++j) L.fcls[j] = n_free ? L.fcls[n_free - 1] : 0;
-    TCCT_CHECK(h_valid >= 0 && h_valid <= H && w_valid >= 0 && w_valid <= W, "layout_decode: valid region %dx%d outside 0..%d x 0..%d", h_valid, w_valid, H, W);
-    TCCT_CHECK(h_valid <= 4096, "layout_decode: h_valid=%d rows (at most 4096: the column sums are int32)", h_valid);
-    TCCT_CHECK((int64_t)W + 63 < (1LL << 31), "layout_decode: W=%d too large", W);
-    TCCT_CHECK((int64_t)H * W * C * 4 < (1LL << 31), "layout_decode: H*W*C = %lld values per image (the pixel offsets are 32 bits)", (long long)H * W * C);
+    ColumnLayout L;
+    int n_free, first_mask;         // first_mask: the decode has no use for it
+    if (column_parse_layout("layout_decode", C, layers, S, free_mask, L, n_free, first_mask)) return -1;
+    if (column_check_limits("layout_decode", ": the column sums are int32", H, W, C, h_valid, w_valid)) return -1;
     TCCT_CHECK(pred && ws && mask && bnd && changed, "layout_decode: pred, ws, mask, bnd and changed are required");
     hipStream_t st = (hipStream_t)stream;
     // `changed` is the one output that is accumulated; an empty valid region launches nothing and zeroes all of them
@@ -318,66 +256,10 @@ extern "C" int tcct_layout_decode(const void* pred, int kind, int B, int H, int 
     }
     if (e != hipSuccess) { tcct_set_error("layout_decode: memset failed"); return -2; }
     if (empty) return 0;
-    const LayoutCall a = {pred, B, H, W, C, L, S, free_mask, h_valid, w_valid, ws, mask, bnd, changed, best, state, st};
-    // per-state register arrays and loops are sized by MAXS
-    const int maxs = layout_maxs(S);
-    if (maxs == 5) layout_decode_kind<5>(a, kind, n_free);
-    else if (maxs == 6) layout_decode_kind<6>(a, kind, n_free);
-    else if (maxs == 10) layout_decode_kind<10>(a, kind, n_free);
-    else layout_decode_kind<16>(a, kind, n_free);
-    TCCT_LAUNCH_OK();
-}
-
-// ----------------------------------------------------------------------- per-image score table under a layout (k_eval_scores of eval.hip with S - 1 surfaces)
-#define LSB 256
-__device__ __forceinline__ long long layout_block_sum(long long v, long long* sm /* LSB */) {
-    __syncthreads();
-    sm[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = LSB / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sm[0];
-}
-// one block per image; table row = [Dice_c | IoU_c | sum |d| per surface | sum d^2 per surface | n_col], sums over the annotated columns
-__global__ void __launch_bounds__(LSB) k_eval_layout_scores(const int32_t* __restrict__ counts, const int32_t* __restrict__ bnd_pred, const int32_t* __restrict__ bnd_lab,
-                                                            int C, int S, int W, int h_valid, int w_valid, double* __restrict__ table) {
-    __shared__ long long sm[LSB];
-    const int b = blockIdx.x, NS = S - 1;
-    double* row = table + (int64_t)b * (2 * C + 2 * NS + 1);
-    if ((int)threadIdx.x < C) {
-        const int32_t* q = counts + ((int64_t)b * C + threadIdx.x) * 3;
-        const long long I = q[0], P = q[1], G = q[2];
-        row[threadIdx.x] = (double)(2 * I + 1) / (double)(P + G + 1);
-        row[C + threadIdx.x] = (double)(I + 1) / (double)(P + G - I + 1);
-    }
-    const int32_t* bp = bnd_pred + (int64_t)b * NS * W;
-    const int32_t* bl = bnd_lab + (int64_t)b * NS * W;
-    // a column is annotated when it lies in the valid region and its label leaves state 0 somewhere
-    long long ncol = 0;
-    for (int x = threadIdx.x; x < w_valid; x += LSB) ncol += bl[x] < h_valid;
-    ncol = layout_block_sum(ncol, sm);
-    if (threadIdx.x == 0) row[2 * C + 2 * NS] = (double)ncol;
-    for (int k = 0; k < NS; ++k) {
-        long long sa = 0, sq = 0;
-        for (int x = threadIdx.x; x < w_valid; x += LSB)
-            if (bl[x] < h_valid) {
-                const long long d = (long long)bp[(int64_t)k * W + x] - (long long)bl[(int64_t)k * W + x];
-                sa += d < 0 ? -d : d;
-                sq += d * d;
-            }
-        sa = layout_block_sum(sa, sm);
-        sq = layout_block_sum(sq, sm);
-        if (threadIdx.x == 0) { row[2 * C + k] = (double)sa; row[2 * C + NS + k] = (double)sq; }
-    }
-}
-extern "C" int tcct_eval_layout_scores(const int32_t* counts, const int32_t* bnd_pred, const int32_t* bnd_lab, int B, int C, int S, int W, int h_valid, int w_valid,
-                                       double* table, tcct_stream_t stream) {
-    TCCT_CHECK(B >= 1 && W >= 1, "eval_layout_scores: empty tensor");
-    TCCT_CHECK(C >= 2 && C <= 16 && S >= 2 && S <= 16, "eval_layout_scores: C=%d classes, S=%d states unsupported (2..16 each)", C, S);
-    TCCT_CHECK(h_valid >= 1 && w_valid >= 1 && w_valid <= W, "eval_layout_scores: valid region %dx%d (W = %d)", h_valid, w_valid, W);
-    TCCT_CHECK(counts && bnd_pred && bnd_lab && table, "eval_layout_scores: counts, bnd_pred, bnd_lab and table are required");
-    hipLaunchKernelGGL(k_eval_layout_scores, dim3((unsigned)B), dim3(LSB), 0, (hipStream_t)stream, counts, bnd_pred, bnd_lab, C, S, W, h_valid, w_valid, table);
+    const dim3 grid((unsigned)((W + 63) / 64), 1, (unsigned)B), block(64);
+    column_dispatch<true>(S, kind, n_free, [&](auto maxs, auto knd, auto nf) {
+        hipLaunchKernelGGL((k_layout_decode<decltype(maxs)::value, decltype(knd)::value, decltype(nf)::value>), grid, block, 0, st, pred, H, W, C, L, S, free_mask,
+                           h_valid, w_valid, ws, mask, bnd, changed, best, state);
+    });
     TCCT_LAUNCH_OK();
 }

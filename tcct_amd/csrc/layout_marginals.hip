@@ -20,21 +20,17 @@
 // A rho that underflows fp32 here is a share below 2^-149 of the sequences through s(y+1) = s'.  The workspace holds per pixel and state s >= 1 ONE float:
 // rho when rho < 0.5, else -u (the sign bit is the tag, so a -0 is u = 0), so that the small one of the pair is the stored one; state 0 has rho = 0, u = 1.
 //
-// Schedule: k_layout_decode's.  A wave owns 64 adjacent columns of one image, a lane owns a column; row addresses are clamped, not guarded; two row batches
-// alternate so that the loads of the next are in flight under the chain of the current one; the layout is wave-uniform (scalar registers), state s loads ITS
-// class from a uniform base.  States >= S are padding with E = 0 (so N(s) = N(S-1), u = 0, rho = 1: they carry nothing and pass everything through), free
-// slots >= n_free re-read the last free class with weight 0.  The softmax denominator counts every class once: the first state of a class and every real
-// free slot.  surf, m2 and logz are accumulated per lane in fp64 (m2 - surf^2 cancels); everything else is fp32.  No atomics: two calls give the same bits.
-#include "common.h"
-#include <type_traits>
+// Layout contract and schedule: column_dp.h.  States >= S are padding with E = 0 (so N(s) = N(S-1), u = 0, rho = 1: they carry nothing and pass everything
+// through), free slots >= n_free re-read the last free class with weight 0.  The softmax denominator counts every class once: the first state of a class and
+// every real free slot.  surf, m2 and logz are accumulated per lane in fp64 (m2 - surf^2 cancels); everything else is fp32.  No atomics: two calls give the
+// same bits.
+#include "column_dp.h"
 
 #define MARG_FLOOR 9.094947017729282e-13f      // 2^-40
-struct MargArgs { int cls[16]; int fcls[14]; };
 // rows per batch, both walks; halved where the posterior or 14 free slots fill the registers (the emissions of a whole batch are computed ahead of its chain)
 template <int MAXS, int NF, bool POST> struct MargCfg {
     static constexpr int R = POST && NF > 2 ? (MAXS <= 10 ? 2 : 1) : (MAXS <= 8 ? 8 : 4) / (POST || NF > 2 ? 2 : 1);
 };
-static inline int marg_maxs(int S) { return S <= 5 ? 5 : (S <= 6 ? 6 : (S <= 10 ? 10 : 16)); }
 
 // the loaded bits as they are: a bf16 value is widened where it is used, not where it is loaded, so that a batch of loads needs no wait of its own
 template <int MAXS, int NF> struct MargRow {
@@ -44,12 +40,6 @@ template <int MAXS, int NF> struct MargRow {
 __device__ __forceinline__ uint32_t marg_ldraw(const float* p) { return __float_as_uint(*p); }
 __device__ __forceinline__ uint32_t marg_ldraw(const bf16* p) { return (uint32_t)*(const uint16_t*)p; }
 template <int KIND> __device__ __forceinline__ float marg_val(uint32_t raw) { return __uint_as_float(KIND == 1 ? raw << 16 : raw); }
-// a false comparison yields the lower clamp (NaN -> -1024), as decode.hip's decode_quant
-__device__ __forceinline__ float marg_clamp(float s) {
-    const float t = s > -1024.f ? s : -1024.f;
-    return t < 1024.f ? t : 1024.f;
-}
-
 // p~ of every state's class (pl), of every free slot (pf, 0 for a padded slot) and the emissions (0 for a padded state)
 template <int MAXS, int KIND, int NF>
 __device__ __forceinline__ void marg_emissions(const MargRow<MAXS, NF>& rw, float inv_tau, int first_mask, int S, int n_free, float (&E)[MAXS], float (&pl)[MAXS],
@@ -57,13 +47,13 @@ __device__ __forceinline__ void marg_emissions(const MargRow<MAXS, NF>& rw, floa
     float t[MAXS], tf[NF ? NF : 1], mx;
 #pragma unroll
     for (int s = 0; s < MAXS; ++s) {
-        t[s] = marg_clamp(marg_val<KIND>(rw.z[s])) * inv_tau;
+        t[s] = column_clamp(marg_val<KIND>(rw.z[s])) * inv_tau;
         mx = s == 0 ? t[0] : fmaxf(mx, t[s]);
     }
     if constexpr (NF > 0) {
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
-            tf[j] = marg_clamp(marg_val<KIND>(rw.zf[j])) * inv_tau;
+            tf[j] = column_clamp(marg_val<KIND>(rw.zf[j])) * inv_tau;
             mx = fmaxf(mx, tf[j]);
         }
     }
@@ -98,7 +88,7 @@ __device__ __forceinline__ void marg_emissions(const MargRow<MAXS, NF>& rw, floa
 
 // KIND: 0 fp32 logits, 1 bf16 logits.  NF: free-class slots (0: the layout has none).  POST: the per-pixel class posterior is written
 template <int MAXS, int KIND, int NF, bool POST>
-__global__ void __launch_bounds__(64) k_layout_marginals(const void* __restrict__ logits, int H, int W, int C, const MargArgs L, int S, int first_mask, int n_free,
+__global__ void __launch_bounds__(64) k_layout_marginals(const void* __restrict__ logits, int H, int W, int C, const ColumnLayout L, int S, int first_mask, int n_free,
                                                          int h_valid, int w_valid, float inv_tau, float* __restrict__ ws, float* __restrict__ surf,
                                                          float* __restrict__ var, float* __restrict__ logz, float* __restrict__ post) {
     constexpr int R = MargCfg<MAXS, NF, POST>::R, NV = MAXS - 1;
@@ -120,18 +110,16 @@ __global__ void __launch_bounds__(64) k_layout_marginals(const void* __restrict_
                 for (int c = 0; c < C; ++c) post[(pix0 + (int64_t)y * W) * C + c] = 0.f;
         return;
     }
-    // image base (uniform) + class (uniform) + pixel offset (32 bits per lane: H * W * C * 4 < 2^31 is checked by the caller).  Every row address is clamped
-    // into the valid rows, so no load sits behind a branch; a row outside re-reads the nearest one and is not used.
     const int esz = (int)sizeof(T) * C;
     const char* img = (const char*)logits + (int64_t)b * H * W * esz;
     const uint32_t col_off = (uint32_t)x * (uint32_t)esz, rsb = (uint32_t)W * (uint32_t)esz;
     auto load_row = [&](Row& rw, int y) {
-        const uint32_t off = (uint32_t)min(max(y, 0), h_valid - 1) * rsb + col_off;
+        const uint32_t off = column_row_offset(y, h_valid, rsb, col_off);
 #pragma unroll
-        for (int s = 0; s < MAXS; ++s) rw.z[s] = marg_ldraw((const T*)((const char*)((const T*)img + L.cls[s]) + off));
+        for (int s = 0; s < MAXS; ++s) rw.z[s] = marg_ldraw(column_at<T>(img, L.cls[s], off));
         if constexpr (NF > 0) {
 #pragma unroll
-            for (int j = 0; j < NF; ++j) rw.zf[j] = marg_ldraw((const T*)((const char*)((const T*)img + L.fcls[j]) + off));
+            for (int j = 0; j < NF; ++j) rw.zf[j] = marg_ldraw(column_at<T>(img, L.fcls[j], off));
         }
     };
     float* __restrict__ wcol = ws + (int64_t)b * H * NV * W + x;       // value (y, s >= 1) of this column is wcol[(y * NV + s - 1) * W]
@@ -314,40 +302,9 @@ __global__ void __launch_bounds__(64) k_layout_marginals(const void* __restrict_
             for (int c = 0; c < C; ++c) post[(pix0 + (int64_t)y * W) * C + c] = 0.f;
 }
 
-struct MargCall {
-    const void* logits; int B, H, W, C; MargArgs L; int S, first_mask, n_free, h_valid, w_valid; float inv_tau; float *ws, *surf, *var, *logz, *post; hipStream_t st;
-};
-template <int MAXS, int KIND, int NF, bool POST>
-static void marg_launch(const MargCall& a) {
-    const dim3 grid((unsigned)((a.W + 63) / 64), 1, (unsigned)a.B), block(64);
-    hipLaunchKernelGGL((k_layout_marginals<MAXS, KIND, NF, POST>), grid, block, 0, a.st, a.logits, a.H, a.W, a.C, a.L, a.S, a.first_mask, a.n_free, a.h_valid, a.w_valid,
-                       a.inv_tau, a.ws, a.surf, a.var, a.logz, a.post);
-}
-template <int MAXS, int KIND, int NF>
-static void marg_post(const MargCall& a) {
-    if (a.post) marg_launch<MAXS, KIND, NF, true>(a);
-    else marg_launch<MAXS, KIND, NF, false>(a);
-}
-template <int MAXS>
-static void marg_kind(const MargCall& a, int kind) {
-    // free slots as in layout_decode.hip: 2 covers one or two lesion classes, 14 everything a layout can hold
-    if (kind == 0) {
-        if (a.n_free == 0) marg_post<MAXS, 0, 0>(a);
-        else if (a.n_free <= 2) marg_post<MAXS, 0, 2>(a);
-        else marg_post<MAXS, 0, 14>(a);
-    } else {
-        if (a.n_free == 0) marg_post<MAXS, 1, 0>(a);
-        else if (a.n_free <= 2) marg_post<MAXS, 1, 2>(a);
-        else marg_post<MAXS, 1, 14>(a);
-    }
-}
-
 extern "C" int64_t tcct_layout_marginals_ws_bytes(int B, int H, int W, int S, int n_free) {
-    if (B < 1 || H < 1 || W < 1 || S < 2 || S > 16 || n_free < 0 || n_free > 14) {
-        tcct_set_error("layout_marginals_ws_bytes: B=%d H=%d W=%d S=%d n_free=%d", B, H, W, S, n_free);
-        return -1;
-    }
-    return (int64_t)B * H * W * (marg_maxs(S) - 1) * (int64_t)sizeof(float);
+    if (!column_ws_args_ok("layout_marginals_ws_bytes", B, H, W, S, n_free)) return -1;
+    return (int64_t)B * H * W * (column_maxs(S) - 1) * (int64_t)sizeof(float);
 }
 
 extern "C" int tcct_layout_marginals(const void* logits, int kind, int B, int H, int W, int C, const int* layers, int S, int free_mask, int h_valid, int w_valid,
@@ -359,27 +316,10 @@ extern "C" int tcct_layout_marginals(const void* logits, int kind, int B, int H,
     TCCT_CHECK(S >= 2 && S <= 16 && layers, "layout_marginals: S=%d states (2..16)", S);
     TCCT_CHECK(free_mask >= 0 && free_mask < (1 << C), "layout_marginals: free_mask=0x%x names a class outside 0..%d", free_mask, C - 1);
     TCCT_CHECK(tau > 0.f && tau <= 3.0e38f, "layout_marginals: tau=%g (a positive temperature)", (double)tau);
-    int seen = free_mask, n_free = 0, first_mask = 0;
-    MargArgs L;
-    for (int s = 0; s < 16; ++s) {
-        const int c = layers[s < S ? s : S - 1];
-        if (s < S) {
-            TCCT_CHECK(c >= 0 && c < C, "layout_marginals: layers[%d]=%d outside 0..%d", s, c, C - 1);
-            TCCT_CHECK(s == 0 || c != layers[s - 1], "layout_marginals: layers[%d] repeats its neighbour (class %d)", s, c);
-            TCCT_CHECK(!((free_mask >> c) & 1), "layout_marginals: class %d is a layer and free", c);
-            if (!((seen >> c) & 1)) first_mask |= 1 << s;
-            seen |= 1 << c;
-        }
-        L.cls[s] = c;
-    }
-    TCCT_CHECK(seen == (1 << C) - 1, "layout_marginals: a class of 0..%d is neither a layer nor free", C - 1);
-    for (int c = 0; c < C; ++c)
-        if ((free_mask >> c) & 1) L.fcls[n_free++] = c;
-    for (int j = n_free; j < 14; ++j) L.fcls[j] = n_free ? L.fcls[n_free - 1] : 0;
-    TCCT_CHECK(h_valid >= 0 && h_valid <= H && w_valid >= 0 && w_valid <= W, "layout_marginals: valid region %dx%d outside 0..%d x 0..%d", h_valid, w_valid, H, W);
-    TCCT_CHECK(h_valid <= 4096, "layout_marginals: h_valid=%d rows (at most 4096, as layout_decode)", h_valid);
-    TCCT_CHECK((int64_t)W + 63 < (1LL << 31), "layout_marginals: W=%d too large", W);
-    TCCT_CHECK((int64_t)H * W * C * 4 < (1LL << 31), "layout_marginals: H*W*C = %lld values per image (the pixel offsets are 32 bits)", (long long)H * W * C);
+    ColumnLayout L;
+    int n_free, first_mask;
+    if (column_parse_layout("layout_marginals", C, layers, S, free_mask, L, n_free, first_mask)) return -1;
+    if (column_check_limits("layout_marginals", ", as layout_decode", H, W, C, h_valid, w_valid)) return -1;
     TCCT_CHECK(logits && ws && surf && var && logz, "layout_marginals: logits, ws, surf, var and logz are required");
     hipStream_t st = (hipStream_t)stream;
     if (h_valid == 0 || w_valid == 0) {         // an empty valid region launches nothing and zeroes every output
@@ -390,29 +330,22 @@ extern "C" int tcct_layout_marginals(const void* logits, int kind, int B, int H,
         if (e != hipSuccess) { tcct_set_error("layout_marginals: memset failed"); return -2; }
         return 0;
     }
-    const MargCall a = {logits, B, H, W, C, L, S, first_mask, n_free, h_valid, w_valid, 1.f / tau, (float*)ws, surf, var, logz, post, st};
-    // per-state register arrays and loops are sized by MAXS
-    const int maxs = marg_maxs(S);
-    if (maxs == 5) marg_kind<5>(a, kind);
-    else if (maxs == 6) marg_kind<6>(a, kind);
-    else if (maxs == 10) marg_kind<10>(a, kind);
-    else marg_kind<16>(a, kind);
+    const dim3 grid((unsigned)((W + 63) / 64), 1, (unsigned)B), block(64);
+    const float inv_tau = 1.f / tau;
+    column_dispatch<false>(S, kind, n_free, [&](auto maxs, auto knd, auto nf) {
+        constexpr int MAXS = decltype(maxs)::value, KIND = decltype(knd)::value, NF = decltype(nf)::value;
+        if (post)
+            hipLaunchKernelGGL((k_layout_marginals<MAXS, KIND, NF, true>), grid, block, 0, st, logits, H, W, C, L, S, first_mask, n_free, h_valid, w_valid, inv_tau,
+                               (float*)ws, surf, var, logz, post);
+        else
+            hipLaunchKernelGGL((k_layout_marginals<MAXS, KIND, NF, false>), grid, block, 0, st, logits, H, W, C, L, S, first_mask, n_free, h_valid, w_valid, inv_tau,
+                               (float*)ws, surf, var, logz, post);
+    });
     TCCT_LAUNCH_OK();
 }
 
 // ----------------------------------------------------------------------- per-image soft scores: the expected surfaces against the label's integer ones
 #define MSB 256
-// fixed order: every thread's strided partial, then a binary tree over the block
-__device__ __forceinline__ double marg_block_sum(double v, double* sm /* MSB */) {
-    __syncthreads();
-    sm[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = MSB / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sm[0];
-}
 // one block per image; table row = [sum |surf - bnd_lab| per surface | sum (surf - bnd_lab)^2 per surface | sum var per surface | n_col]
 __global__ void __launch_bounds__(MSB) k_eval_soft_scores(const float* __restrict__ surf, const float* __restrict__ var, const int32_t* __restrict__ bnd_lab, int S, int W,
                                                           int h_valid, int w_valid, double* __restrict__ table) {
@@ -425,7 +358,7 @@ __global__ void __launch_bounds__(MSB) k_eval_soft_scores(const float* __restric
     // a column is annotated when it lies in the valid region and its label leaves state 0 somewhere (6b)
     double ncol = 0.0;
     for (int x = threadIdx.x; x < w_valid; x += MSB) ncol += bl[x] < h_valid ? 1.0 : 0.0;
-    ncol = marg_block_sum(ncol, sm);
+    ncol = block_tree_sum<double, MSB>(ncol, sm);
     if (threadIdx.x == 0) row[3 * NS] = ncol;
     for (int k = 0; k < NS; ++k) {
         double sa = 0.0, sq = 0.0, sv = 0.0;
@@ -436,9 +369,9 @@ __global__ void __launch_bounds__(MSB) k_eval_soft_scores(const float* __restric
                 sq += d * d;
                 sv += (double)vp[(int64_t)k * W + x];
             }
-        sa = marg_block_sum(sa, sm);
-        sq = marg_block_sum(sq, sm);
-        sv = marg_block_sum(sv, sm);
+        sa = block_tree_sum<double, MSB>(sa, sm);
+        sq = block_tree_sum<double, MSB>(sq, sm);
+        sv = block_tree_sum<double, MSB>(sv, sm);
         if (threadIdx.x == 0) { row[k] = sa; row[NS + k] = sq; row[2 * NS + k] = sv; }
     }
 }

@@ -96,6 +96,22 @@ def table_width(n_class, layout=None):
     return 4 * n_class - 1 if layout is None else 2 * n_class + 2 * (layout.n_states - 1) + 1
 
 
+def _valid(valid, H, W):
+    """valid = (h_valid, w_valid), default the whole image"""
+    return (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+
+
+def _table_rows(who, table, row, B, wid, device):
+    """where B images' scores go: table[row : row + B] of a contiguous CUDA fp64 [N, wid] table, or a fresh [B, wid] without one"""
+    if table is None:
+        table, row = torch.empty((B, wid), device=device, dtype=torch.float64), 0
+    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == wid and table.is_contiguous()):
+        raise TcctError(f'{who}: table must be a contiguous CUDA fp64 [N, {wid}]')
+    if row < 0 or row + B > table.shape[0]:
+        raise TcctError(f'{who}: rows {row}..{row + B} do not fit a table of {table.shape[0]} images')
+    return table[row:row + B]
+
+
 def _check(pred, lab, n_class, valid):
     if not (torch.is_tensor(pred) and torch.is_tensor(lab) and pred.is_cuda and lab.is_cuda):
         raise TcctError('eval_counts: prediction and labels must be CUDA tensors (no CPU fallback)')
@@ -108,8 +124,7 @@ def _check(pred, lab, n_class, valid):
     want = (B, H, W) if kind == 2 else (B, H, W, n_class)
     if tuple(pred.shape) != want:
         raise TcctError(f'eval_counts: prediction {tuple(pred.shape)} does not match labels {tuple(lab.shape)} with {n_class} classes (expected {want})')
-    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
-    return kind, B, H, W, hv, wv
+    return (kind, B, H, W) + _valid(valid, H, W)
 
 
 def eval_counts(pred, lab, n_class, valid=None, want_mask=False, want_boundaries=True):
@@ -141,7 +156,7 @@ def ordered_decode(logits, n_class, valid=None, want_best=False):
     if logits.dim() != 4 or logits.shape[3] != n_class:
         raise TcctError(f'ordered_decode: logits {tuple(logits.shape)} are not NHWC [B,H,W,{n_class}]')
     B, H, W, C = logits.shape
-    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    hv, wv = _valid(valid, H, W)
     dev = logits.device
     take = torch.empty((B, H, W), device=dev, dtype=torch.uint8 if C <= 8 else torch.int16)
     mask = torch.empty((B, H, W), device=dev, dtype=torch.uint8)
@@ -170,7 +185,7 @@ def layout_decode(pred, layout, valid=None, want_best=False, want_state=False):
     if pred.dim() != (3 if kind == 2 else 4) or (kind != 2 and pred.shape[3] != C):
         raise TcctError(f'layout_decode: prediction {tuple(pred.shape)} is neither NHWC [B,H,W,{C}] logits nor a uint8 [B,H,W] class map')
     B, H, W = pred.shape[:3]
-    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    hv, wv = _valid(valid, H, W)
     dev = pred.device
     nbytes = lib.layout_decode_ws_bytes(B, H, W, S, len(layout.free))
     if nbytes < 0:
@@ -208,7 +223,7 @@ def layout_marginals(logits, layout, valid=None, tau=1.0, want_post=False):
     if logits.dim() != 4 or logits.shape[3] != C:
         raise TcctError(f'layout_marginals: logits {tuple(logits.shape)} are not NHWC [B,H,W,{C}]')
     B, H, W = logits.shape[:3]
-    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    hv, wv = _valid(valid, H, W)
     dev = logits.device
     nbytes = lib.layout_marginals_ws_bytes(B, H, W, S, len(layout.free))
     if nbytes < 0:
@@ -233,14 +248,7 @@ def eval_soft_scores(surf, var, bnd_lab, valid, table=None, row=0):
     if not ok or surf.dtype != torch.float32 or var.dtype != torch.float32 or bnd_lab.dtype != torch.int32 or not (surf.shape == var.shape == bnd_lab.shape):
         raise TcctError('eval_soft_scores: surf, var fp32 [B,S-1,W] and bnd_lab int32 [B,S-1,W] on the device expected')
     B, NS, W = surf.shape
-    wid = 3 * NS + 1
-    if table is None:
-        table, row = torch.empty((B, wid), device=surf.device, dtype=torch.float64), 0
-    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == wid and table.is_contiguous()):
-        raise TcctError(f'eval_soft_scores: table must be a contiguous CUDA fp64 [N, {wid}]')
-    if row < 0 or row + B > table.shape[0]:
-        raise TcctError(f'eval_soft_scores: rows {row}..{row + B} do not fit a table of {table.shape[0]} images')
-    out = table[row:row + B]
+    out = _table_rows('eval_soft_scores', table, row, B, 3 * NS + 1, surf.device)
     lib.eval_soft_scores(surf.contiguous(), var.contiguous(), bnd_lab.contiguous(), B, NS + 1, W, int(valid[0]), int(valid[1]), out)
     return out
 
@@ -267,16 +275,10 @@ def eval_layout_scores(counts, bnd_pred, bnd_lab, layout, valid, table=None, row
     """counts as `eval_counts` returns them (decoded mask against the label), bnd_pred / bnd_lab the surfaces `layout_decode` gives for prediction and label
     -> fp64 [B, 2C + 2(S-1) + 1] = Dice_c | IoU_c | sum |d| per surface | sum d^2 per surface | n_col (include/tcct_hip.h).  `table`, `row` as `eval_scores`."""
     B, C = counts.shape[0], counts.shape[1]
-    S, wid = layout.n_states, table_width(C, layout)
+    S = layout.n_states
     if C != layout.n_class or tuple(bnd_pred.shape) != tuple(bnd_lab.shape) or tuple(bnd_pred.shape[:2]) != (B, S - 1):
         raise TcctError(f'eval_layout_scores: counts {tuple(counts.shape)}, surfaces {tuple(bnd_pred.shape)} / {tuple(bnd_lab.shape)} do not fit {layout!r}')
-    if table is None:
-        table, row = torch.empty((B, wid), device=counts.device, dtype=torch.float64), 0
-    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == wid and table.is_contiguous()):
-        raise TcctError(f'eval_layout_scores: table must be a contiguous CUDA fp64 [N, {wid}]')
-    if row < 0 or row + B > table.shape[0]:
-        raise TcctError(f'eval_layout_scores: rows {row}..{row + B} do not fit a table of {table.shape[0]} images')
-    out = table[row:row + B]
+    out = _table_rows('eval_layout_scores', table, row, B, table_width(C, layout), counts.device)
     lib.eval_layout_scores(counts, bnd_pred.contiguous(), bnd_lab.contiguous(), B, C, S, bnd_pred.shape[2], int(valid[0]), int(valid[1]), out)
     return out
 
@@ -285,17 +287,8 @@ def eval_scores(counts, bnd_pred, bnd_lab, valid, table=None, row=0):
     """counts / bnd_* as eval_counts returns them, valid = (h_valid, w_valid) -> fp64 [B, 4C-1] (module docstring of eval.hip / include/tcct_hip.h for the
     columns).  With `table` (fp64 [N, 4C-1], contiguous) the rows go to table[row : row + B] and that slice is returned."""
     B, C = counts.shape[0], counts.shape[1]
-    if bnd_pred is not None:
-        W = bnd_pred.shape[2]
-    else:
-        W = int(valid[1])
-    if table is None:
-        table, row = torch.empty((B, table_width(C)), device=counts.device, dtype=torch.float64), 0
-    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == table_width(C) and table.is_contiguous()):
-        raise TcctError(f'eval_scores: table must be a contiguous CUDA fp64 [N, {table_width(C)}]')
-    if row < 0 or row + B > table.shape[0]:
-        raise TcctError(f'eval_scores: rows {row}..{row + B} do not fit a table of {table.shape[0]} images')
-    out = table[row:row + B]
+    W = bnd_pred.shape[2] if bnd_pred is not None else int(valid[1])
+    out = _table_rows('eval_scores', table, row, B, table_width(C), counts.device)
     lib.eval_scores(counts, bnd_pred, bnd_lab, B, C, W, int(valid[0]), int(valid[1]), out)
     return out
 

@@ -215,6 +215,26 @@ def test_eval_scores_exact(name):
     assert np.array_equal(got[2:2 + B], ref) and (got[:2] == -1).all() and (got[2 + B:] == -1).all()
 
 
+@pytest.mark.parametrize('shape', [SHAPES[1], SHAPES[3]], ids=lambda s: 'x'.join(map(str, s)))
+def test_eval_scores_is_the_layout_scores_of_the_identity(shape):
+    """one kernel behind both entry points: with S = C states tcct_eval_layout_scores gives the bytes of tcct_eval_scores.  One image's label never leaves
+    class 0 (every boundary at h_valid), so n_col counts fewer columns than w_valid there"""
+    from tcct_amd._lib import lib
+    B, H, W, C, hv, wv = shape
+    _, cnt, bp, bl = _case(shape)[3]['u8']
+    bl = bl.copy()
+    bl[1] = hv
+    d = [torch.from_numpy(a.astype(np.int32)).cuda() for a in (cnt, bp, bl)]
+    G = Guard()
+    t0, t1 = G.new((B, 4 * C - 1), torch.float64, 'scores'), G.new((B, 4 * C - 1), torch.float64, 'layout_scores')
+    lib.eval_scores(d[0], d[1], d[2], B, C, W, hv, wv, t0)
+    lib.eval_layout_scores(d[0], d[1], d[2], B, C, C, W, hv, wv, t1)
+    got = t0.cpu().numpy()
+    assert np.array_equal(got.view(np.uint8), t1.cpu().numpy().view(np.uint8))
+    assert np.array_equal(got, R.scores(cnt, bp, bl, (hv, wv))) and got[1, 4 * C - 2] == 0 and 0 < got[0, 4 * C - 2] < wv
+    G.check()
+
+
 def test_evaluator_accumulates_batches():
     from tcct_amd import evalm
     shape = SHAPES[1]
