@@ -10,7 +10,10 @@ typedef __hip_bfloat16 bf16;
 
 void tcct_set_error(const char* fmt, ...);
 // launch census (tests only: "did the row-stream / chain kernel really run for this shape?"): host-side counters bumped next to the launch
-enum { TCCT_CENSUS_CHAIN33 = 0, TCCT_CENSUS_WGRADK_STREAM = 1, TCCT_CENSUS_WGRAD33_STREAM = 2, TCCT_CENSUS_FWD33_STREAM = 3, TCCT_CENSUS_N = 8 };
+// (pointwise families: k_pw_fwd counts once under PW_FWD and once under PW_FWD_NT0 + its N-tiles per block, 1..5; the C3 first-layer launches are not counted)
+enum { TCCT_CENSUS_CHAIN33 = 0, TCCT_CENSUS_WGRADK_STREAM = 1, TCCT_CENSUS_WGRAD33_STREAM = 2, TCCT_CENSUS_FWD33_STREAM = 3,
+       TCCT_CENSUS_PW_FWD = 4, TCCT_CENSUS_PW_FWD_NT0 = 4, TCCT_CENSUS_PW_FWD2 = 10, TCCT_CENSUS_PW_BWD = 11, TCCT_CENSUS_PW_WGRAD = 12,
+       TCCT_CENSUS_PW_WGRAD_SMALLN = 13, TCCT_CENSUS_PW_WGRAD_SMALLN_MFMA = 14, TCCT_CENSUS_PWF_FWD = 15, TCCT_CENSUS_PWF_WGRAD = 16, TCCT_CENSUS_N = 24 };
 void tcct_census_hit(int which);
 int tcct_skip_zero_fill();      // 1: the caller guarantees accumulation outputs are already zero (tcct_set_outputs_prezeroed)
 

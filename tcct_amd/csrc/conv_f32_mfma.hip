@@ -439,6 +439,7 @@ extern "C" int tcct_pwf_fwd(const float* x, const float* w, const float* bias, f
     const int gy = (N / 32 + PF_NTB - 1) / PF_NTB;
     int64_t gx = 1024 / gy;
     if (gx > tiles) gx = tiles;
+    tcct_census_hit(TCCT_CENSUS_PWF_FWD);
     hipLaunchKernelGGL(k_pwf_mfma, dim3((unsigned)gx, gy), dim3(CFB), 0, (hipStream_t)stream, x, w, bias, y, M, K, N, transposed, tiles);
     TCCT_LAUNCH_OK();
 }
@@ -542,6 +543,7 @@ extern "C" int tcct_pwf_wgrad(const float* x, const float* dy, float* dw, float*
     if (gx < 32) gx = 32;
     if (gx > (tiles + 7) / 8) gx = (tiles + 7) / 8;        // >= 8 tiles per block: every block ends with same-address atomics on all of dw
     if (gx < 1) gx = 1;
+    tcct_census_hit(TCCT_CENSUS_PWF_WGRAD);
     tcct_launch<k_pwf_wgrad, 160 * 1024>(dim3((unsigned)gx, gy), dim3(CFB), lds, st, x, dy, dw, dbias, M, K, N, tiles);
     TCCT_LAUNCH_OK();
 }

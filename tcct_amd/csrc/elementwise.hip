@@ -22,8 +22,10 @@ extern "C" int tcct_set_outputs_prezeroed(int on) { g_skip_zero = on ? 1 : 0; re
 extern "C" int tcct_version(void) { return 100; }
 static int64_t g_census[TCCT_CENSUS_N];
 void tcct_census_hit(int which) { __atomic_fetch_add(&g_census[which], 1, __ATOMIC_RELAXED); }
-/* launches of kernel family `which` (0 k_conv32_chain33, 1 k_conv32_wgradk_stream, 2 k_conv32_wgrad33_stream, 3 k_conv32_fwd33_stream) since the last reset;
- * reset != 0 clears the counter after reading.  Host-side bookkeeping only (tests assert which kernel a shape was routed to). */
+/* launches of kernel family `which` (0 k_conv32_chain33, 1 k_conv32_wgradk_stream, 2 k_conv32_wgrad33_stream, 3 k_conv32_fwd33_stream; the pointwise GEMMs: 4 k_pw_fwd,
+ * 5..9 k_pw_fwd with 1..5 N-tiles per block, 10 k_pw_fwd2, 11 k_pw_bwd, 12 k_pw_wgrad, 13 k_pw_wgrad_smalln, 14 k_pw_wgrad_smalln_mfma, 15 k_pwf_mfma, 16 k_pwf_wgrad;
+ * the C3 first-layer instantiations are not counted) since the last reset; reset != 0 clears the counter after reading.  Host-side bookkeeping only (tests assert
+ * which kernel a shape was routed to). */
 extern "C" int64_t tcct_kernel_census(int which, int reset) {
     if (which < 0 || which >= TCCT_CENSUS_N) return -1;
     const int64_t v = __atomic_load_n(&g_census[which], __ATOMIC_RELAXED);

@@ -506,6 +506,8 @@ static int pw_fwd_impl(const void* x, const float* w, const float* bias, void* y
 #undef PW_NT4
 #undef PW_GO
     TCCT_CHECK(hit, "pw_fwd: no kernel for %d N-tiles per block (stats %d)", NT, stats != nullptr);
+    tcct_census_hit(TCCT_CENSUS_PW_FWD);            // (behind the launch: the refusals above return before it)
+    tcct_census_hit(TCCT_CENSUS_PW_FWD_NT0 + NT);
     TCCT_LAUNCH_OK();
 }
 
@@ -760,13 +762,14 @@ static int pw_wgrad_impl(const void* x, const void* x2, int K1, const void* dy, 
     TCCT_CHECK(ldy >= N && ldy % 8 == 0, "pw_wgrad: ldy=%lld must be a multiple of 8 and >= N=%d", (long long)ldy, N);
     TCCT_CHECK(K % 32 == 0 && N % 32 == 0 && K >= 32 && N >= 32 && N <= 160 && K <= 1024, "pw_wgrad: unsupported K=%d N=%d", K, N);
     hipStream_t st = (hipStream_t)stream;
-    if (!tcct_skip_zero_fill() && hipMemsetAsync(dw, 0, sizeof(float) * (size_t)N * K, st) != hipSuccess) { tcct_set_error("pw_wgrad: memset failed"); return -2; }
-    if (dbias && !tcct_skip_zero_fill() && hipMemsetAsync(dbias, 0, sizeof(float) * N, st) != hipSuccess) { tcct_set_error("pw_wgrad: memset failed"); return -2; }
     const int NT = N / 32, ktiles = K / 32;
     const int KTB = (ktiles % 2 == 0 && NT <= 2) ? 2 : 1;       // <= 5 accumulators per wave next to the prefetch registers (round 6: two slabs at 96 / 128 outputs -- to re-read dy
                                                                 // half as often: stage 1's `aggregate` reads its 113 MB dy six times -- spill 22 / 139 VGPRs at two blocks per CU: not offered)
     const int gy = ktiles / KTB;
     TCCT_CHECK(!x2 || K1 % (KTB * 32) == 0, "pw_wgrad_cat2: K1=%d must be a multiple of %d for this shape", K1, KTB * 32);
+    // (nothing touches the device before the last check: a refused call leaves dw / dbias as they were)
+    if (!tcct_skip_zero_fill() && hipMemsetAsync(dw, 0, sizeof(float) * (size_t)N * K, st) != hipSuccess) { tcct_set_error("pw_wgrad: memset failed"); return -2; }
+    if (dbias && !tcct_skip_zero_fill() && hipMemsetAsync(dbias, 0, sizeof(float) * N, st) != hipSuccess) { tcct_set_error("pw_wgrad: memset failed"); return -2; }
     // row strides: S mod 256 in {64,192} keeps the 4-pixel x 64-byte footprint of a transposing read on distinct banks
     const int SX = KTB == 1 ? 64 : 192;
     const int SD = 2 * N + ((NT & 1) ? 0 : 64);
@@ -784,6 +787,7 @@ static int pw_wgrad_impl(const void* x, const void* x2, int K1, const void* dy, 
     if (tiles <= 1024) { int small = 128 / gy; if (small < 16) small = 16; if (gx > small) gx = small; }
     if (gx > tiles) gx = (int)tiles;
     if (gx < 1) gx = 1;
+    tcct_census_hit(TCCT_CENSUS_PW_WGRAD);
 #define WL(NTV, KV) tcct_launch<k_pw_wgrad<NTV, KV>, 160 * 1024>(dim3(gx, gy), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, dw, dbias, M, K, N, SX, SD, (const bf16*)x2, K1, ldy, C3Geom{})
     if (KTB == 2) { switch (NT) { case 1: WL(1, 2); break; default: WL(2, 2); break; } }      // (KTB == 2 only with NT <= 2, N <= 160 checked above)
     else { switch (NT) { case 1: WL(1, 1); break; case 2: WL(2, 1); break; case 3: WL(3, 1); break; case 4: WL(4, 1); break; default: WL(5, 1); break; } }
@@ -1413,6 +1417,7 @@ static int pw_bwd_impl(const void* x, const void* dy, const float* w, const void
     // step, where the tensors are not the same two buffers over and over, it was slower: k_pw_bwd 2.46 -> 2.57 ms per step; two per CU stay)
     int64_t gx = 256 * per_cu;
     if (gx > tiles) gx = tiles;
+    tcct_census_hit(TCCT_CENSUS_PW_BWD);
     row->launch(dim3((unsigned)gx), dim3(PWB), lds, st, (const bf16*)x, (const bf16*)dy, w, (const bf16*)res, (bf16*)dx, (bf16*)dx_plain, dw, dbias, M, bn);
     TCCT_LAUNCH_OK();
 }
@@ -1771,6 +1776,7 @@ static int pw_fwd2_launch(const void* x, const void* x2, const float* w, const f
     // (as for k_pw_bwd: one block per CU won by 3-10 % in the micro-benchmark and lost inside the step -- the statistics variants by 60 %)
     int64_t gx = 256 * per_cu;
     if (gx > tiles) gx = tiles;
+    tcct_census_hit(TCCT_CENSUS_PW_FWD2);
     row->launch(dim3((unsigned)gx), dim3(PWB), lds, (hipStream_t)stream, (const bf16*)x, (const bf16*)x2, w, bias, (bf16*)y, M, stats, stat_pre, pr);
     TCCT_LAUNCH_OK();
 }
@@ -1975,11 +1981,14 @@ k_pw_wgrad_smalln_mfma(const bf16* __restrict__ x, const float* __restrict__ dy,
 extern "C" int tcct_pw_wgrad_smalln(const void* x, const void* dy, float* dw, float* dbias, int64_t M, int K, int N, int x_dtype,
                                     int dy_dtype, tcct_stream_t stream) {
     TCCT_CHECK(K % 4 == 0 && K >= 4 && K <= 256 && N >= 1 && N <= 8, "pw_wgrad_smalln: unsupported K=%d N=%d", K, N);
+    // (before anything is cleared: a refused call leaves dw / dbias as they were)
+    TCCT_CHECK((x_dtype == TCCT_BF16 && (dy_dtype == TCCT_F32 || dy_dtype == TCCT_BF16)) || (x_dtype == TCCT_F32 && dy_dtype == TCCT_F32), "pw_wgrad_smalln: bad dtypes");
     hipStream_t st = (hipStream_t)stream;
     if (!tcct_skip_zero_fill() && hipMemsetAsync(dw, 0, sizeof(float) * N * K, st) != hipSuccess) { tcct_set_error("pw_wgrad_smalln: memset failed"); return -2; }
     if (dbias && !tcct_skip_zero_fill() && hipMemsetAsync(dbias, 0, sizeof(float) * N, st) != hipSuccess) { tcct_set_error("pw_wgrad_smalln: memset failed"); return -2; }
     if (K == 32 && x_dtype == TCCT_BF16 && dy_dtype == TCCT_F32) {
         const int64_t tiles = (M + PW_P - 1) / PW_P;
+        tcct_census_hit(TCCT_CENSUS_PW_WGRAD_SMALLN_MFMA);
         hipLaunchKernelGGL(k_pw_wgrad_smalln_mfma, dim3((unsigned)(tiles < 512 ? tiles : 512)), dim3(PWB), 0, st, (const bf16*)x, (const float*)dy, dw,
                            dbias, M, N);
         TCCT_LAUNCH_OK();
@@ -1993,5 +2002,6 @@ extern "C" int tcct_pw_wgrad_smalln(const void* x, const void* dy, float* dw, fl
     else if (x_dtype == TCCT_F32 && dy_dtype == TCCT_F32) SL(float, float);
     else { tcct_set_error("pw_wgrad_smalln: bad dtypes"); return -1; }
 #undef SL
+    tcct_census_hit(TCCT_CENSUS_PW_WGRAD_SMALLN);
     TCCT_LAUNCH_OK();
 }

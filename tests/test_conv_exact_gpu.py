@@ -21,7 +21,7 @@ Entries covered (csrc/conv_mfma.hip, conv_chain.hip, conv.hip, the conv32f_* ent
   tcct_conv2d_fwd, tcct_conv2d_dgrad, tcct_conv2d_wgrad                    test_node_generic
   tcct_conv32_fwd_mode, tcct_conv32_wgrad_mode: set and restored by every test that names a mode.
 The default dispatch (no mode, no force) at the smallest maps that reach the row streams by themselves: test_default_dispatch_*.
-Left out: tcct_pwf_fwd / tcct_pwf_wgrad of conv_f32_mfma.hip (the pointwise family, a follow-up)."""
+tcct_pwf_fwd / tcct_pwf_wgrad of conv_f32_mfma.hip and the whole pointwise family (tcct_pw_*): tests/pw_ref.py, tests/test_pw_exact_gpu.py, tests/test_pw_rounding_gpu.py."""
 import contextlib
 import functools
 
