@@ -13,7 +13,10 @@ void tcct_set_error(const char* fmt, ...);
 // (pointwise families: k_pw_fwd counts once under PW_FWD and once under PW_FWD_NT0 + its N-tiles per block, 1..5; the C3 first-layer launches are not counted)
 enum { TCCT_CENSUS_CHAIN33 = 0, TCCT_CENSUS_WGRADK_STREAM = 1, TCCT_CENSUS_WGRAD33_STREAM = 2, TCCT_CENSUS_FWD33_STREAM = 3,
        TCCT_CENSUS_PW_FWD = 4, TCCT_CENSUS_PW_FWD_NT0 = 4, TCCT_CENSUS_PW_FWD2 = 10, TCCT_CENSUS_PW_BWD = 11, TCCT_CENSUS_PW_WGRAD = 12,
-       TCCT_CENSUS_PW_WGRAD_SMALLN = 13, TCCT_CENSUS_PW_WGRAD_SMALLN_MFMA = 14, TCCT_CENSUS_PWF_FWD = 15, TCCT_CENSUS_PWF_WGRAD = 16, TCCT_CENSUS_N = 24 };
+       TCCT_CENSUS_PW_WGRAD_SMALLN = 13, TCCT_CENSUS_PW_WGRAD_SMALLN_MFMA = 14, TCCT_CENSUS_PWF_FWD = 15, TCCT_CENSUS_PWF_WGRAD = 16,
+       // depthwise 3x3 (dwconv.hip): k_dw_fwd with one column per thread at stride 1 / at stride 2 / with four columns per thread, k_dw_dgrad_s2, k_dw_wgrad with one / two columns per thread
+       TCCT_CENSUS_DW_FWD_S1 = 17, TCCT_CENSUS_DW_FWD_S2 = 18, TCCT_CENSUS_DW_FWD_CPT4 = 19, TCCT_CENSUS_DW_DGRAD_S2 = 20, TCCT_CENSUS_DW_WGRAD = 21,
+       TCCT_CENSUS_DW_WGRAD_CPT2 = 22, TCCT_CENSUS_N = 24 };
 void tcct_census_hit(int which);
 int tcct_skip_zero_fill();      // 1: the caller guarantees accumulation outputs are already zero (tcct_set_outputs_prezeroed)
 

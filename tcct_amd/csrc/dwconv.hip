@@ -353,12 +353,14 @@ static void dw_fwd_launch(const void* x, const float* w, const float* bias, void
         dw_geometry(N, Ho, Wo, C, VEC, 1024, 32, segh, wblocks, hstrips, 4);
         dim3 g4((unsigned)((int64_t)N * wblocks * hstrips));
         hipLaunchKernelGGL((k_dw_fwd<T, VEC, 1, FLIP, (VEC == 4 ? 4 : 1), MODE>), g4, dim3(DB), 0, st, (const T*)x, w, bias, (T*)y, N, H, W, C, Ho, Wo, add_input, segh, wblocks, hstrips, (const T*)res, stats, xab);
+        tcct_census_hit(TCCT_CENSUS_DW_FWD_CPT4);          // (behind the launch: the entries' refusals return before it)
         return;
     }
     dw_geometry(N, Ho, Wo, C, VEC, 1024, 32, segh, wblocks, hstrips);
     dim3 g((unsigned)((int64_t)N * wblocks * hstrips)), b(DB);
     if (stride == 1) hipLaunchKernelGGL((k_dw_fwd<T, VEC, 1, FLIP, 1, MODE>), g, b, 0, st, (const T*)x, w, bias, (T*)y, N, H, W, C, Ho, Wo, add_input, segh, wblocks, hstrips, (const T*)res, stats, xab);
     else hipLaunchKernelGGL((k_dw_fwd<T, VEC, 2, FLIP, 1, MODE>), g, b, 0, st, (const T*)x, w, bias, (T*)y, N, H, W, C, Ho, Wo, add_input, segh, wblocks, hstrips, (const T*)res, stats, xab);
+    tcct_census_hit(stride == 1 ? TCCT_CENSUS_DW_FWD_S1 : TCCT_CENSUS_DW_FWD_S2);
 }
 
 extern "C" int tcct_dwconv3x3_fwd(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int C,
@@ -559,6 +561,7 @@ static int dw_dgrad_impl(const void* dy, const float* w, const void* res, void* 
     dim3 g((unsigned)((int64_t)N * wblocks * hstrips)), b(DB);
     if (vec == 4) { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_dw_dgrad_s2<T, 4>), g, b, 0, st, (const T*)dy, w, (T*)dx, N, H, W, C, Ho, Wo, segh, wblocks, hstrips, (const T*)res)); }
     else { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_dw_dgrad_s2<T, 1>), g, b, 0, st, (const T*)dy, w, (T*)dx, N, H, W, C, Ho, Wo, segh, wblocks, hstrips, (const T*)res)); }
+    tcct_census_hit(TCCT_CENSUS_DW_DGRAD_S2);
     TCCT_LAUNCH_OK();
 }
 extern "C" int tcct_dwconv3x3_dgrad(const void* dy, const float* w, void* dx, int N, int H, int W, int C, int stride,
@@ -778,6 +781,7 @@ static int dw_wgrad_impl(const void* x, const void* dy, float* dw, float* dbias,
                                     N, H, W, C, Ho, Wo, segh, wblocks, hstrips, xab);
         else hipLaunchKernelGGL((k_dw_wgrad<bf16, 4, 1, 2>), dim3((unsigned)((int64_t)N * wblocks * hstrips)), dim3(DB), lds, st, (const bf16*)x, (const bf16*)dy, dw, dbias,
                                 N, H, W, C, Ho, Wo, segh, wblocks, hstrips, xab);
+        tcct_census_hit(TCCT_CENSUS_DW_WGRAD_CPT2);
         TCCT_LAUNCH_OK();
     }
     dw_geometry(N, Ho, Wo, C, vec, 256, 128, segh, wblocks, hstrips);
@@ -789,5 +793,6 @@ static int dw_wgrad_impl(const void* x, const void* dy, float* dw, float* dbias,
     else { TCCT_DISPATCH(dtype, if (stride == 1) DWG(1, 1); else DWG(1, 2)); }
 #undef DWG
 #undef DWGX
+    tcct_census_hit(TCCT_CENSUS_DW_WGRAD);
     TCCT_LAUNCH_OK();
 }
