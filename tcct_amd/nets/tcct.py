@@ -272,11 +272,10 @@ class ConvRelPosEnc(nn.Module):
         self.channel_splits = [x * Ch for x in self.head_splits]
 
 
-class FactorAtt_ConvRelPosEnc(nn.Module):
-    """reference nets/tcct.py:289-341: the factorised-attention token mixer the reference keeps commented out in
-    MHCABlock (tcct.py:436-449).  qkv / proj are the pointwise GEMMs; softmax over the tokens, the per-head K^T V and Q (K^T V)
-    contractions and the convolutional relative position term are the `tcct_fatt_*` / `tcct_dwk_*` kernels.  The crpe head splits
-    (2+3+3) need num_heads = 8; attn_drop / proj_drop are 0 in the reference (DROP_RATE, tcct.py:26)."""
+class _AttentionMixer(nn.Module):
+    """qkv Linear -> the token mixer `ops.<mixer>` with the shared crpe -> proj Linear: the two attention variants the reference keeps
+    commented out in MHCABlock.  The crpe head splits (2+3+3) need num_heads = 8; attn_drop / proj_drop are 0 in the reference (DROP_RATE, tcct.py:26)."""
+    mixer = None
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, shared_crpe=None):
         super().__init__()
@@ -291,35 +290,24 @@ class FactorAtt_ConvRelPosEnc(nn.Module):
         if sum(self.crpe.channel_splits) != x.shape[-1]:
             raise ValueError(f'crpe head splits {self.crpe.head_splits} do not cover {self.num_heads} heads')
         qkv = ops.conv2d(x, self.qkv.weight, self.qkv.bias)
-        return ops.factor_att(qkv, size, self.num_heads, self.scale, self.crpe.conv_list)
+        return getattr(ops, self.mixer)(qkv, size, self.num_heads, self.scale, self.crpe.conv_list)
 
     def forward(self, x, size):
         return ops.conv2d(self.mix(x, size), self.proj.weight, self.proj.bias)
 
 
-class HydraAttention(nn.Module):
-    """reference nets/tcct.py:343-403: the other token mixer the reference keeps commented out in MHCABlock (tcct.py:435-441).  Same parameters
-    as FactorAtt_ConvRelPosEnc (qkv / proj pointwise GEMMs, the shared crpe); between them q and k are normalised per head and token, k * v is summed
-    over the tokens per channel and multiplied onto q (`tcct_hydra_*` kernels), plus the same convolutional relative position term (`tcct_dwk_*`).
-    The crpe head splits (2+3+3) need num_heads = 8; attn_drop / proj_drop are 0 in the reference (DROP_RATE, tcct.py:26)."""
+class FactorAtt_ConvRelPosEnc(_AttentionMixer):
+    """reference nets/tcct.py:289-341: the factorised-attention token mixer (commented out in MHCABlock, tcct.py:436-449).  qkv / proj are the
+    pointwise GEMMs; softmax over the tokens, the per-head K^T V and Q (K^T V) contractions and the convolutional relative position term are the
+    `tcct_fatt_*` / `tcct_dwk_*` kernels."""
+    mixer = 'factor_att'
 
-    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, shared_crpe=None):
-        super().__init__()
-        self.num_heads = num_heads
-        self.scale = qk_scale or (dim // num_heads) ** -0.5
-        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
-        self.proj = nn.Linear(dim, dim)
-        self.crpe = shared_crpe
 
-    def mix(self, x, size):
-        """everything up to (not including) the output projection: tokens [B,N,C] -> [B,N,C]"""
-        if sum(self.crpe.channel_splits) != x.shape[-1]:
-            raise ValueError(f'crpe head splits {self.crpe.head_splits} do not cover {self.num_heads} heads')
-        qkv = ops.conv2d(x, self.qkv.weight, self.qkv.bias)
-        return ops.hydra_att(qkv, size, self.num_heads, self.scale, self.crpe.conv_list)
-
-    def forward(self, x, size):
-        return ops.conv2d(self.mix(x, size), self.proj.weight, self.proj.bias)
+class HydraAttention(_AttentionMixer):
+    """reference nets/tcct.py:343-403: the other token mixer (commented out in MHCABlock, tcct.py:435-441).  Same parameters as FactorAtt_ConvRelPosEnc;
+    between qkv and proj, q and k are normalised per head and token, k * v is summed over the tokens per channel and multiplied onto q (`tcct_hydra_*`
+    kernels), plus the same convolutional relative position term (`tcct_dwk_*`)."""
+    mixer = 'hydra_att'
 
 
 class Mlp(nn.Module):
@@ -625,23 +613,38 @@ class MPUpBlock(nn.Module):
         u = ops.bilinear(y, (x1.shape[1] * 2, x1.shape[2] * 2), True, residual=x2)
         return _conv(self.post[0], u)
 
-    def forward_through(self, x1, x2, t32, aux=None):
-        """t32(x2 + forward(x1, x2)) for the LAST decoder block, whose own output nobody else reads (FTC.forward, reference tcct.py:1031-1040):
-        resize, `post`, the skip add and `t32` as ONE GEMM with composed weights (ops.up_skip_conv_t32), or None when that form does not apply.
-        aux: the level-0 head when the caller needs only ITS output of g0 -> returns the tuple (fp32 logits NHWC, resized y) instead"""
-        p, t = self.post[0], t32
-        probe = torch.empty((x1.shape[0], x1.shape[1], x1.shape[2], self.prep[0].out_channels), dtype=x1.dtype, device='meta')    # shape / dtype only: no device memory
+    def _composes(self, x1, x2, t32, aux=None):
+        """whether the composed tail applies (through `aux` as well when one is given), decided from shapes and dtypes alone: no device memory"""
+        p = self.post[0]
+        probe = torch.empty((x1.shape[0], x1.shape[1], x1.shape[2], self.prep[0].out_channels), dtype=x1.dtype, device='meta')
         # (train mode -- or inference with the fused epilogues: the composition needs no statistics, round 6)
-        if not ((self.prep[1].training or (ops.INFER_FUSE and not torch.is_grad_enabled())) and ops.up_skip_conv_t32_ok(probe, x2, p.weight, p.bias, t.weight, t.bias)):
+        if not (self.prep[1].training or (ops.INFER_FUSE and not torch.is_grad_enabled())):
+            return False
+        if aux is None:
+            return ops.up_skip_conv_t32_ok(probe, x2, p.weight, p.bias, t32.weight, t32.bias)
+        return ops.up_skip_conv_t32_aux_ok(probe, x2, p.weight, p.bias, t32.weight, t32.bias, aux.weight, aux.bias)
+
+    def forward_through(self, x1, x2, t32):
+        """t32(x2 + forward(x1, x2)) for the LAST decoder block, whose own output nobody else reads (FTC.forward, reference tcct.py:1031-1040):
+        resize, `post`, the skip add and `t32` as ONE GEMM with composed weights (ops.up_skip_conv_t32), or None when that form does not apply."""
+        if not self._composes(x1, x2, t32):
             return None
         y = _conv_bn(self.prep[0], self.prep[1], x1, post='lrelu')
-        if aux is not None and ops.up_skip_conv_t32_aux_ok(probe, x2, p.weight, p.bias, t.weight, t.bias, aux.weight, aux.bias):
-            # nothing but the aux head reads g0 in this step: (fp32 logits, what `feats` would rebuild g0 from) -- g0 is never written
-            if ops.TAIL_AUX_LOW:    # ... and the resize is taken of the n_class-channel product at the low resolution: up(y) is never written either
-                return ops.up_skip_conv_t32_aux_low(y, x2, p.weight, p.bias, t.weight, t.bias, aux.weight, aux.bias, True), ('y', y.detach())
-            lg, v = ops.up_skip_conv_t32_aux(y, x2, p.weight, p.bias, t.weight, t.bias, aux.weight, aux.bias, True)
-            return lg, ('v', v)
-        return ops.up_skip_conv_t32(y, x2, p.weight, p.bias, t.weight, t.bias, True)
+        return ops.up_skip_conv_t32(y, x2, self.post[0].weight, self.post[0].bias, t32.weight, t32.bias, True)
+
+    def forward_through_aux(self, x1, x2, t32, aux):
+        """aux(forward_through(x1, x2, t32)) for a step in which nothing but the level-0 head `aux` reads g0, which is then never written:
+        (fp32 logits NHWC, rebuild) with rebuild() -> g0 (no gradient) for `FTC.feats`, or None when that form does not apply."""
+        if not self._composes(x1, x2, t32, aux):
+            return None
+        p, t = self.post[0], t32
+        y = _conv_bn(self.prep[0], self.prep[1], x1, post='lrelu')
+        if ops.TAIL_AUX_LOW:    # the resize is taken of the n_class-channel product at the low resolution: up(y) is never written either
+            src = y.detach()
+            return (ops.up_skip_conv_t32_aux_low(y, x2, p.weight, p.bias, t.weight, t.bias, aux.weight, aux.bias, True),
+                    lambda: ops.up_skip_conv_t32_from_y(src, x2, p.weight, p.bias, t.weight, t.bias))
+        lg, v = ops.up_skip_conv_t32_aux(y, x2, p.weight, p.bias, t.weight, t.bias, aux.weight, aux.bias, True)
+        return lg, lambda: ops.up_skip_conv_t32_from_v(v, x2, p.weight, p.bias, t.weight, t.bias)
 
 
 class FTC(nn.Module):
@@ -805,12 +808,11 @@ class FTC(nn.Module):
             # level 0: post, `x_0 + y_0` and t324 as one GEMM (u, d0, s0 never written) -- and through aux0 as well when the feature-polarization
             # loss is off (nothing else reads g0 then; `feats` rebuilds it on demand)
             compose = (self.compose_heads and not self.eager_feats) or mho
-            g0 = self.dec4.forward_through(d1, f[0], self.t324, aux=self.aux0 if compose else None)
-            if isinstance(g0, tuple):
-                y0_direct, (kind, src) = g0
-                skip0, pw, tw = f[0], self.dec4.post[0], self.t324
-                rebuild = ops.up_skip_conv_t32_from_v if kind == 'v' else ops.up_skip_conv_t32_from_y
-                g0 = lambda: rebuild(src, skip0, pw.weight, pw.bias, tw.weight, tw.bias)      # noqa: E731
+            through_aux = self.dec4.forward_through_aux(d1, f[0], self.t324, self.aux0) if compose else None
+            if through_aux is not None:
+                y0_direct, g0 = through_aux       # g0: the closure that rebuilds it on demand
+            else:
+                g0 = self.dec4.forward_through(d1, f[0], self.t324)
             if g0 is None:
                 d0, s0 = self.dec4(d1, f[0], with_sum=True, want_plain=False)      # only x_0 + y_0 is read below: d0 is never written
                 g0 = _conv(self.t324, s0)

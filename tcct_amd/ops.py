@@ -1132,18 +1132,47 @@ def _pw_backward(x, dz, w, wsrc, bsrc):
     return dx, dw, db
 
 
+def _pw_backward_gelu(x1, dz, w, wsrc, bsrc):
+    """-> (dx1, dw, db) of z = gelu(x1) W^T + bias, bf16, from ONE pass over dz with GELU and its derivative applied while the tiles are staged
+    (tcct_pw_bwd_gelu): neither h = gelu(x1) nor dh exist in HBM"""
+    K, Cout = x1.shape[-1], w.shape[0]
+    dx1 = torch.empty_like(x1)
+    dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
+    lib.pw_bwd_gelu(x1, dz, w, dx1, dw, db, x1.numel() // K, K, Cout)
+    return dx1, dw, db
+
+
+def _sum2(ga, gb):
+    """the contiguous sum of two optional output gradients of one shape; the one that is there when the other is None; None without either"""
+    if ga is None or gb is None:
+        g = gb if ga is None else ga
+        return None if g is None else _c(g)
+    dz = torch.empty_like(gb)
+    lib.add(_c(ga), _c(gb), dz, dz.numel(), dtype_code(dz.dtype))
+    return dz
+
+
+MLP_GELU_FUSE = True         # False: GELU as its own pass between fc1 and fc2 (round-3 form; A/B timing)
+
+
 class _LinearResidual(_FastFunction):
-    """res + scale[b] * (x W^T + bias) on tokens [B,N,C] (Mlp.fc2 + DropPath scale + residual add in the GEMM epilogue)"""
+    """res + scale[b] * (x W^T + bias) on tokens [B,N,C] (Mlp.fc2 + DropPath scale + residual add in the GEMM epilogue).
+    gelu: res + scale[b] * (gelu(x) W^T + bias) with x the PRE-activation of Mlp.fc1 (reference nets/tcct.py:29-53,468): GELU is applied while the GEMM
+    kernels stage their tiles (tcct_pw_fwd_gelu_residual / _pw_backward_gelu), so neither h = gelu(x) nor dh exist in HBM -- bit-identical to
+    act(x, 'gelu') followed by the plain form (same formula, same bf16 roundings), two tensor passes fewer forward and three fewer backward."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, res, scale):
+    def forward(ctx, x, w, bias, res, scale, gelu=False):
         _chk(x, w, bias, res, scale)
         B, Nt, K = x.shape
         Cout = w.shape[0]
         y = torch.empty((B, Nt, Cout), device=x.device, dtype=x.dtype)
-        lib.pw_fwd_residual(x, w, bias, res, scale, Nt, y, None, B * Nt, K, Cout)
+        if gelu:
+            lib.pw_fwd_gelu_residual(x, w, bias, res, scale, Nt, y, B * Nt, K, Cout)
+        else:
+            lib.pw_fwd_residual(x, w, bias, res, scale, Nt, y, None, B * Nt, K, Cout)
         ctx.save_for_backward(x, w)
-        ctx.scale, ctx.params = scale, (w, bias)
+        ctx.scale, ctx.params, ctx.gelu = scale, (w, bias), gelu
         return y
 
     @staticmethod
@@ -1151,42 +1180,8 @@ class _LinearResidual(_FastFunction):
         x, w = ctx.saved_tensors
         wsrc, bsrc = ctx.params
         dy = _c(dy)
-        dx, dw, db = _pw_backward(x, _scale_rows(dy, ctx.scale), w, wsrc, bsrc)
-        return dx, _ret(dw, wsrc), _ret(db, bsrc), dy, None
-
-
-MLP_GELU_FUSE = True         # False: GELU as its own pass between fc1 and fc2 (round-3 form; A/B timing)
-
-
-class _GeluLinearResidual(_FastFunction):
-    """res + scale[b] * (gelu(x1) W^T + bias) on tokens [B,N,C] with x1 the PRE-activation of Mlp.fc1 (reference nets/tcct.py:29-53,468): GELU is applied
-    while the GEMM kernels stage their tiles (tcct_pw_fwd_gelu_residual / tcct_pw_bwd_gelu), so neither h = gelu(x1) nor dh exist in HBM -- bit-identical
-    to act(x1, 'gelu') followed by linear_residual (same formula, same bf16 roundings), two tensor passes fewer forward and three fewer backward."""
-
-    @staticmethod
-    def forward(ctx, x1, w, bias, res, scale):
-        _chk(x1, w, bias, res, scale)
-        B, Nt, K = x1.shape
-        Cout = w.shape[0]
-        y = torch.empty((B, Nt, Cout), device=x1.device, dtype=x1.dtype)
-        lib.pw_fwd_gelu_residual(x1, w, bias, res, scale, Nt, y, B * Nt, K, Cout)
-        ctx.save_for_backward(x1, w)
-        ctx.scale, ctx.params = scale, (w, bias)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x1, w = ctx.saved_tensors
-        wsrc, bsrc = ctx.params
-        dy = _c(dy)
-        B, Nt, K = x1.shape
-        Cout, M = w.shape[0], B * Nt
-        dz = _scale_rows(dy, ctx.scale)
-        dx1 = torch.empty_like(x1)
-        dw = _grad_out(wsrc, tuple(w.shape))
-        db = _grad_out(bsrc)
-        lib.pw_bwd_gelu(x1, dz, w, dx1, dw, db, M, K, Cout)
-        return dx1, _ret(dw, wsrc), _ret(db, bsrc), dy, None
+        dx, dw, db = (_pw_backward_gelu if ctx.gelu else _pw_backward)(x, _scale_rows(dy, ctx.scale), w, wsrc, bsrc)
+        return dx, _ret(dw, wsrc), _ret(db, bsrc), dy, None, None
 
 
 class _MlpTail(_FastFunction):
@@ -1219,9 +1214,7 @@ class _MlpTail(_FastFunction):
         dz = _scale_rows(dt2, ctx.scale)
         w1s = _param_of(w1p)
         w2s = _param_of(w2p)
-        dy1 = torch.empty_like(y1)
-        dw2, db2 = _grad_out(w2s, tuple(w2.shape)), _grad_out(bias2p)
-        lib.pw_bwd_gelu(y1, dz, w2, dy1, dw2, db2, M, K, K)
+        dy1, dw2, db2 = _pw_backward_gelu(y1, dz, w2, w2s, bias2p)
         dt1 = torch.empty_like(t1)
         dw1, db1 = _grad_out(w1s, tuple(w1.shape)), _grad_out(bias1p)
         dg2, dbeta2 = _grad_out(g2p), _grad_out(b2p)
@@ -1251,7 +1244,7 @@ def gelu_linear_residual_ok(x1, w, bias, res):
 
 def gelu_linear_residual(x1, w, bias, res, scale=None):
     """res + scale[b] * Linear(gelu(x1)); check gelu_linear_residual_ok first"""
-    return _GeluLinearResidual.apply(x1, w, bias, res, scale)
+    return _LinearResidual.apply(x1, w, bias, res, scale, True)
 
 
 class _Conv1x1AndSum(_FastFunction):
@@ -1276,12 +1269,7 @@ class _Conv1x1AndSum(_FastFunction):
         wsrc, bsrc = ctx.params
         if gd is None and gs is None:
             return None, None, None, None
-        if gd is None or gs is None:
-            dz = _c(gd if gs is None else gs)
-        else:
-            dz = torch.empty_like(gs)
-            lib.add(_c(gd), _c(gs), dz, dz.numel(), dtype_code(dz.dtype))
-        dx, dw, db = _pw_backward(x, dz, w, wsrc, bsrc)
+        dx, dw, db = _pw_backward(x, _sum2(gd, gs), w, wsrc, bsrc)
         return dx, _ret(dw, wsrc), _ret(db, bsrc), (None if gs is None else _c(gs))
 
 
@@ -1332,10 +1320,7 @@ class _UpSkipConv(_FastFunction):
                 dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
                 lib.pw_bwd_residual2_sum(u, gd, gs, w, gs, dskip, du, dw, db, M, C, Cout)
             else:
-                dz = gs
-                if gd is not None:
-                    dz = torch.empty_like(gs)
-                    lib.add(gd, gs, dz, dz.numel(), dtype_code(dz.dtype))
+                dz = _sum2(gd, gs)
                 if _pw_bwd_ok(u, dz, C, C, Cout, 1, 1, 1, 0, 0):       # both input gradients and the weight / bias gradients from ONE pass over dz
                     dw, db = _grad_out(wsrc, tuple(w.shape)), _grad_out(bsrc)
                     lib.pw_bwd_residual2(u, dz, w, gs, dskip, du, dw, db, M, C, Cout)
@@ -1365,6 +1350,53 @@ def up_skip_conv(y, skip, w, bias, align_corners=True, want_plain=True):
 TAIL_COMPOSE = True      # False: resize + add, post convolution (+ sum), t324 as three kernels (round-3 form; A/B timing)
 
 
+def _resize_to(y, skip, align):
+    """v = y resized to the height and width of skip (bilinear, tcct_bilinear_fwd)"""
+    N_, H, W_, C = y.shape
+    v = torch.empty_like(skip)
+    lib.bilinear_fwd(y, v, N_, H, W_, C, skip.shape[1], skip.shape[2], int(align), dtype_code(y.dtype))
+    return v
+
+
+def _tail_g0(v, skip, w1, b1, w2, b2):
+    """-> (g0, wc): g0 = t32(post(v + skip) + skip) as ONE 64 -> 32 GEMM over the never-materialised [v | skip] with the composed weight wc [32, 64]
+    (tcct_tail_compose)"""
+    wc = torch.empty((32, 64), device=v.device, dtype=torch.float32)
+    c = torch.empty(32, device=v.device, dtype=torch.float32)
+    lib.tail_compose(w1, b1, w2, b2, wc, c)
+    g = torch.empty_like(skip)
+    lib.pw_fwd_cat2(v, skip, 32, wc, c, g, v.numel() // 32, 64, 32, None, 0)
+    return g, wc
+
+
+def _tail_compose3(w1, b1, w2, b2, w3, b3, pad8=False):
+    """the composed weights of aux(t32(post(v + skip) + skip)) (tcct_tail_compose3) -> (wcc [nc, 64] over [v | skip], its halves wa and wb [nc, 32, 1, 1],
+    the bias ccc [nc], wa8).  pad8: wa is the first nc rows of wa8 [8, 32, 1, 1], whose other rows are zero; else wa8 is None"""
+    nc, f32 = w3.shape[0], dict(device=w3.device, dtype=torch.float32)
+    wcc = torch.empty((nc, 64), **f32)
+    wa8 = torch.zeros((8, 32, 1, 1), **f32) if pad8 else None
+    wa, wb = (wa8[:nc] if pad8 else torch.empty((nc, 32, 1, 1), **f32)), torch.empty((nc, 32, 1, 1), **f32)
+    ccc = torch.empty(nc, **f32)
+    lib.tail_compose3(w1, b1, w2, b2, w3, b3, nc, wcc, wa, wb, ccc)
+    return wcc, wa, wb, ccc, wa8
+
+
+def _composed_wgrad(pairs, params, decompose, keep):
+    """The parameter gradients of a composed head, on the weight-gradient stream: per (x, g, rows, wants_bias) of `pairs` the small-N sum g^T x [nc, 32]
+    into a zeroed buffer (the one with wants_bias also sums g into the composed bias' gradient), then decompose(nc, sums..., bias sum, *destinations of
+    params).  keep: every tensor the side stream reads, kept alive until it is joined.  -> what backward returns for params, in their order"""
+    nc, dev = pairs[0][1].shape[-1], pairs[0][0].device
+    F32_, BF_ = dtype_code(torch.float32), dtype_code(pairs[0][0].dtype)
+    with _wgrad_stream(_slot_written(*params), *keep):
+        sums = [ZERO.get((nc, 32), torch.float32, dev) for _ in pairs]
+        dbias = ZERO.get((nc,), torch.float32, dev)
+        for (x, g, rows, wants_bias), dw in zip(pairs, sums):
+            lib.pw_wgrad_smalln(x, g, dw, dbias if wants_bias else None, rows, 32, nc, BF_, F32_)
+        outs = [_grad_out(p, tuple(p.shape)) for p in params]
+        decompose(nc, *sums, dbias, *outs)
+    return tuple(_ret(o, p) for o, p in zip(outs, params))
+
+
 class _UpSkipConvT32(_FastFunction):
     """g0 = t32(post(up(y) + skip) + skip) for the LAST decoder block (reference nets/tcct.py:908-914, :1031, :1035-1040) as ONE 64 -> 32 GEMM over the
     never-materialised concatenation [up(y) | skip] with composed weights (csrc/decoder_tail.hip): u, d0 and s0 are not written, the backward pass is
@@ -1375,14 +1407,8 @@ class _UpSkipConvT32(_FastFunction):
         _chk(y, skip, w1, b1, w2, b2)
         N_, H, W_, C = y.shape
         _, Ho, Wo, _ = skip.shape
-        dev = y.device
-        v = torch.empty_like(skip)
-        lib.bilinear_fwd(y, v, N_, H, W_, C, Ho, Wo, int(align), dtype_code(y.dtype))
-        wc = torch.empty((32, 64), device=dev, dtype=torch.float32)
-        c = torch.empty(32, device=dev, dtype=torch.float32)
-        lib.tail_compose(w1, b1, w2, b2, wc, c)
-        g = torch.empty_like(skip)
-        lib.pw_fwd_cat2(v, skip, 32, wc, c, g, N_ * Ho * Wo, 64, 32, None, 0)
+        v = _resize_to(y, skip, align)
+        g, wc = _tail_g0(v, skip, w1, b1, w2, b2)
         ctx.save_for_backward(v, skip, wc)
         ctx.params = (w1, b1, w2, b2)
         ctx.cfg = (N_, H, W_, C, Ho, Wo, int(align))
@@ -1431,12 +1457,8 @@ class _UpSkipConvT32Aux(_FastFunction):
         N_, H, W_, C = y.shape
         _, Ho, Wo, _ = skip.shape
         dev, nc = y.device, w3.shape[0]
-        v = torch.empty_like(skip)
-        lib.bilinear_fwd(y, v, N_, H, W_, C, Ho, Wo, int(align), dtype_code(y.dtype))
-        wcc = torch.empty((nc, 64), device=dev, dtype=torch.float32)
-        wa, wb = torch.empty((nc, 32, 1, 1), device=dev, dtype=torch.float32), torch.empty((nc, 32, 1, 1), device=dev, dtype=torch.float32)
-        ccc = torch.empty(nc, device=dev, dtype=torch.float32)
-        lib.tail_compose3(w1, b1, w2, b2, w3, b3, nc, wcc, wa, wb, ccc)
+        v = _resize_to(y, skip, align)
+        wcc, wa, wb, ccc, _ = _tail_compose3(w1, b1, w2, b2, w3, b3)
         lg = torch.empty((N_, Ho, Wo, nc), device=dev, dtype=torch.float32)
         lib.pw_fwd_cat2_f32(v, skip, 32, wcc, ccc, lg, N_ * Ho * Wo, 64, nc)
         ctx.save_for_backward(v, skip, wa, wb)
@@ -1459,15 +1481,9 @@ class _UpSkipConvT32Aux(_FastFunction):
         lib.conv2d_dgrad(dl, wb, dskip, N_, Ho, Wo, 32, nc, 1, 1, 0, 0, F32_, BF_)
         dy = torch.empty((N_, H, W_, C), device=dev, dtype=v.dtype)
         lib.bilinear_bwd(dv, dy, N_, H, W_, C, Ho, Wo, align, BF_)
-        params = (w1, b1, w2, b2, w3, b3)
-        with _wgrad_stream(_slot_written(*params), v, skip, dl, wa, wb):
-            dwa, dwb = ZERO.get((nc, 32), torch.float32, dev), ZERO.get((nc, 32), torch.float32, dev)
-            dccc = ZERO.get((nc,), torch.float32, dev)
-            lib.pw_wgrad_smalln(v, dl, dwa, dccc, M, 32, nc, BF_, F32_)
-            lib.pw_wgrad_smalln(skip, dl, dwb, None, M, 32, nc, BF_, F32_)
-            outs = [_grad_out(p, tuple(p.shape)) for p in params]
-            lib.tail_compose3_bwd(w1, b1, w2, b2, w3, nc, dwa, dwb, dccc, *outs)
-        return (dy, dskip) + tuple(_ret(o, p) for o, p in zip(outs, params)) + (None,)
+        dparams = _composed_wgrad([(v, dl, M, True), (skip, dl, M, False)], ctx.params, lambda *a: lib.tail_compose3_bwd(w1, b1, w2, b2, w3, *a),
+                                  keep=(v, skip, dl, wa, wb))
+        return (dy, dskip) + dparams + (None,)
 
 
 class _UpSkipConvT32AuxLow(_FastFunction):
@@ -1485,11 +1501,8 @@ class _UpSkipConvT32AuxLow(_FastFunction):
         _, Ho, Wo, _ = skip.shape
         dev, nc = y.device, w3.shape[0]
         F32_ = dtype_code(torch.float32)
-        wcc = torch.empty((nc, 64), device=dev, dtype=torch.float32)
-        wa8 = torch.zeros((8, 32, 1, 1), device=dev, dtype=torch.float32)        # rows >= n_class stay zero: the low-resolution product has 8 channels (16-byte taps)
-        wa, wb = wa8[:nc], torch.empty((nc, 32, 1, 1), device=dev, dtype=torch.float32)
-        ccc = torch.empty(nc, device=dev, dtype=torch.float32)
-        lib.tail_compose3(w1, b1, w2, b2, w3, b3, nc, wcc, wa, wb, ccc)
+        # wa8: rows >= n_class stay zero: the low-resolution product has 8 channels (16-byte taps)
+        wcc, wa, wb, ccc, wa8 = _tail_compose3(w1, b1, w2, b2, w3, b3, pad8=True)
         lg = torch.empty((N_, Ho, Wo, nc), device=dev, dtype=torch.float32)
         if HEAD_UPADD and align and Ho == 2 * H and Wo == 2 * W_:
             z8 = torch.empty((N_, H, W_, 8), device=dev, dtype=torch.float32)
@@ -1527,15 +1540,9 @@ class _UpSkipConvT32AuxLow(_FastFunction):
         else:
             dskip = torch.empty_like(skip)
             lib.conv2d_dgrad(dl, wb, dskip, N_, Ho, Wo, 32, nc, 1, 1, 0, 0, F32_, BF_)
-        params = ctx.params
-        with _wgrad_stream(_slot_written(*params), y, skip, dl, dz, wa, wb):
-            dwa, dwb = ZERO.get((nc, 32), torch.float32, dev), ZERO.get((nc, 32), torch.float32, dev)
-            dccc = ZERO.get((nc,), torch.float32, dev)
-            lib.pw_wgrad_smalln(y, dz, dwa, None, N_ * H * W_, 32, nc, BF_, F32_)
-            lib.pw_wgrad_smalln(skip, dl, dwb, dccc, N_ * Ho * Wo, 32, nc, BF_, F32_)
-            outs = [_grad_out(p, tuple(p.shape)) for p in params]
-            lib.tail_compose3_bwd(params[0], params[1], params[2], params[3], params[4], nc, dwa, dwb, dccc, *outs)
-        return (dy, dskip) + tuple(_ret(o, p) for o, p in zip(outs, params)) + (None,)
+        dparams = _composed_wgrad([(y, dz, N_ * H * W_, False), (skip, dl, N_ * Ho * Wo, True)], ctx.params,
+                                  lambda *a: lib.tail_compose3_bwd(*ctx.params[:5], *a), keep=(y, skip, dl, dz, wa, wb))
+        return (dy, dskip) + dparams + (None,)
 
 
 HEAD_UPADD = True       # False: the resized low-resolution product is added by its own pass (A/B timing)
@@ -1553,10 +1560,7 @@ def up_skip_conv_t32_aux_low(y, skip, w1, b1, w2, b2, w3, b3, align_corners=True
 def up_skip_conv_t32_from_y(y, skip, w1, b1, w2, b2, align_corners=True):
     """g0 of the composed tail from the un-resized y (no gradient): what `FTC.feats` needs when the step itself never resized y"""
     with torch.no_grad():
-        N_, H, W_, C = y.shape
-        v = torch.empty_like(skip)
-        lib.bilinear_fwd(y, v, N_, H, W_, C, skip.shape[1], skip.shape[2], int(align_corners), dtype_code(y.dtype))
-    return up_skip_conv_t32_from_v(v, skip, w1, b1, w2, b2)
+        return _tail_g0(_resize_to(y, skip, align_corners), skip, w1, b1, w2, b2)[0]
 
 
 TAIL_AUX = True       # False: the composed tail stops at g0, aux0 stays its own kernels (A/B timing)
@@ -1575,12 +1579,7 @@ def up_skip_conv_t32_aux(y, skip, w1, b1, w2, b2, w3, b3, align_corners=True):
 def up_skip_conv_t32_from_v(v, skip, w1, b1, w2, b2):
     """g0 of the composed tail from an already resized v (no gradient): what `FTC.feats` needs when the step itself skipped g0"""
     with torch.no_grad():
-        wc = torch.empty((32, 64), device=v.device, dtype=torch.float32)
-        c = torch.empty(32, device=v.device, dtype=torch.float32)
-        lib.tail_compose(w1, b1, w2, b2, wc, c)
-        g = torch.empty_like(skip)
-        lib.pw_fwd_cat2(v, skip, 32, wc, c, g, v.numel() // 32, 64, 32, None, 0)
-    return g
+        return _tail_g0(v, skip, w1, b1, w2, b2)[0]
 
 
 class _HeadThroughT32(_FastFunction):
@@ -1607,17 +1606,12 @@ class _HeadThroughT32(_FastFunction):
         s, wh = ctx.saved_tensors
         wt, bt, wa, ba = ctx.params
         N_, H, W_, _ = s.shape
-        nc, dev = wa.shape[0], s.device
+        nc = wa.shape[0]
         dl = _as(dl, torch.float32)
         F32_, BF_ = dtype_code(torch.float32), dtype_code(s.dtype)
         ds = torch.empty_like(s)
         lib.conv2d_dgrad(dl, wh, ds, N_, H, W_, 32, nc, 1, 1, 0, 0, F32_, BF_)
-        with _wgrad_stream(_slot_written(*ctx.params), s, dl, wh):
-            dwh, dch = ZERO.get((nc, 32), torch.float32, dev), ZERO.get((nc,), torch.float32, dev)
-            lib.pw_wgrad_smalln(s, dl, dwh, dch, N_ * H * W_, 32, nc, BF_, F32_)
-            outs = [_grad_out(p, tuple(p.shape)) for p in ctx.params]
-            lib.head_compose_bwd(wt, bt, wa, nc, dwh, dch, *outs)
-        return (ds,) + tuple(_ret(o, p) for o, p in zip(outs, ctx.params))
+        return (ds,) + _composed_wgrad([(s, dl, N_ * H * W_, True)], ctx.params, lambda *a: lib.head_compose_bwd(wt, bt, wa, *a), keep=(s, dl, wh))
 
 
 HEAD_COMPOSE = True       # False: t32x and aux_i stay two convolutions at levels 1-3 (A/B timing)
@@ -1651,7 +1645,7 @@ def linear_residual(x, w, bias, res, scale=None):
           and w.shape[0] <= 160 and bias is not None and res.shape == x.shape[:-1] + (w.shape[0],))
     if not ok:
         return residual(res, conv2d(x, w, bias), scale)
-    return _LinearResidual.apply(x, w, bias, res, scale)
+    return _LinearResidual.apply(x, w, bias, res, scale, False)
 
 
 class _PwCat2(_FastFunction):
@@ -2459,6 +2453,20 @@ def bn2_add_act(xa, bnA, xb, bnB, pre_act='lrelu', act_kind='gelu'):
                             ACT[act_kind])
 
 
+def _layernorm_backward(x, dy, dskip, gamma, beta, mr):
+    """-> (dx, dgamma, dbeta) of y = LayerNorm(x) with statistics mr; dskip (or None): a gradient that reaches x around the normalisation, added inside the
+    kernel (tcct_layernorm_bwd_add)"""
+    C = x.shape[-1]
+    M = x.numel() // C
+    dx = torch.empty_like(x)
+    dg, db = _grad_out(gamma), _grad_out(beta)
+    if dskip is None:
+        lib.layernorm_bwd(x, dy, dx, M, C, gamma, mr, dg, db, dtype_code(x.dtype))
+    else:
+        lib.layernorm_bwd_add(x, dy, _as(dskip, x.dtype), dx, M, C, gamma, mr, dg, db, dtype_code(x.dtype))
+    return dx, dg, db
+
+
 class _LayerNorm(_FastFunction):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, fork=False):
@@ -2480,16 +2488,7 @@ class _LayerNorm(_FastFunction):
         x, gamma, mr = ctx.saved_tensors
         if dy is None:
             return dskip, None, None, None, None
-        dy = _as(dy, x.dtype)
-        C = x.shape[-1]
-        M = x.numel() // C
-        dx = torch.empty_like(x)
-        dg = _grad_out(gamma)
-        db = _grad_out(ctx.beta_param)
-        if dskip is None:
-            lib.layernorm_bwd(x, dy, dx, M, C, gamma, mr, dg, db, dtype_code(x.dtype))
-        else:
-            lib.layernorm_bwd_add(x, dy, _as(dskip, x.dtype), dx, M, C, gamma, mr, dg, db, dtype_code(x.dtype))
+        dx, dg, db = _layernorm_backward(x, _as(dy, x.dtype), dskip, gamma, ctx.beta_param, mr)
         return dx, _ret(dg, gamma), _ret(db, ctx.beta_param), None, None
 
 
@@ -2755,21 +2754,14 @@ class _LnMetaPoolResidualLn(_FastFunction):
         b1, b2 = ctx.beta
         eps1, scale = ctx.cfg
         B, N, C = t.shape
-        dc = dtype_code(t.dtype)
         dg2 = db2 = None
         if dcur is not None:
-            dcur = _as(dcur, t.dtype)
-            dt1 = torch.empty_like(t)
-            dg2, db2 = _grad_out(g2), _grad_out(b2)
-            if dres is None:
-                lib.layernorm_bwd(y, dcur, dt1, B * N, C, g2, mr2, dg2, db2, dc)
-            else:
-                lib.layernorm_bwd_add(y, dcur, _as(dres, t.dtype), dt1, B * N, C, g2, mr2, dg2, db2, dc)
+            dt1, dg2, db2 = _layernorm_backward(y, _as(dcur, t.dtype), dres, g2, b2, mr2)
         else:
             dt1 = _as(dres, t.dtype)
         dt = torch.empty_like(t)
         dg1, db1 = _grad_out(g1), _grad_out(b1)
-        lib.ln_metapool_residual_bwd(t, dt1, dt, B, N, C, g1, eps1, scale, dg1, db1, dc)
+        lib.ln_metapool_residual_bwd(t, dt1, dt, B, N, C, g1, eps1, scale, dg1, db1, dtype_code(t.dtype))
         return dt, _ret(dg1, g1), _ret(db1, b1), None, None, _ret(dg2, g2), _ret(db2, b2), None
 
 
@@ -2799,6 +2791,50 @@ def metapool(x):
     return _MetaPool.apply(x)
 
 
+def _att_check(name, qkv, H, W, heads, wb):
+    """the shapes both attention nodes need: qkv [B, H*W, 3C], C a multiple of heads, Ch = C / heads a multiple of 4, the crpe windows covering C"""
+    B, N, C3 = qkv.shape
+    C = C3 // 3
+    if C * 3 != C3 or H * W != N or C % heads or (C // heads) % 4:
+        raise TcctError(f'{name}: qkv {tuple(qkv.shape)} does not fit size ({H},{W}) / heads {heads} (Ch must be a multiple of 4)')
+    if sum(w.shape[0] for w in wb[0::2]) != C:
+        raise TcctError(f'{name}: the crpe window splits do not add up to the channel count')
+
+
+def _crpe_forward(qkv, H, W, wb):
+    """cv [B,N,C] = the depthwise K x K windows of ConvRelPosEnc over the channel groups of v, read in place out of qkv (wb: weight, bias per window)"""
+    B, N, C3 = qkv.shape
+    C, dt = C3 // 3, dtype_code(qkv.dtype)
+    cv = torch.empty((B, N, C), device=qkv.device, dtype=qkv.dtype)
+    off = 0
+    for w, b in zip(wb[0::2], wb[1::2]):
+        Cg, K = w.shape[0], w.shape[2]
+        lib.dwk_strided_fwd(qkv[0, 0, 2 * C + off:], 3 * C, w, b, cv[0, 0, off:], C, B, H, W, Cg, K, 0, 0, dt)
+        off += Cg
+    return cv
+
+
+def _crpe_backward(qkv, dcv, dqkv, H, W, wb):
+    """the windows' backward: the gradient through cv is ADDED to the v third of dqkv; -> what backward returns for wb"""
+    B, N, C3 = qkv.shape
+    C, dt = C3 // 3, dtype_code(qkv.dtype)
+    grads, off = [], 0
+    for w, b in zip(wb[0::2], wb[1::2]):
+        Cg, K = w.shape[0], w.shape[2]
+        lib.dwk_strided_fwd(dcv[0, 0, off:], C, w, None, dqkv[0, 0, 2 * C + off:], 3 * C, B, H, W, Cg, K, 1, 1, dt)
+        dw = _grad_out(w)
+        db = _grad_out(b) if b is not None else None
+        lib.dwk_strided_wgrad(qkv[0, 0, 2 * C + off:], 3 * C, dcv[0, 0, off:], C, dw, db, B, H, W, Cg, K, dt)
+        grads += [_ret(dw, w), _ret(db, b)]
+        off += Cg
+    return tuple(grads)
+
+
+def _crpe_wb(crpe_convs):
+    """the nn.Conv2d list of ConvRelPosEnc -> [weight, bias, weight, bias, ...]"""
+    return [p for m in crpe_convs for p in (m.weight, m.bias)]
+
+
 class _FactorAtt(_FastFunction):
     """FactorAtt_ConvRelPosEnc.forward between the qkv and proj Linear layers (reference nets/tcct.py:316-331 + ConvRelPosEnc.forward
     :265-287): out [B,N,C] = scale * q (softmax_N(k)^T v) + q * crpe(v), qkv [B,N,3C] (dormant in stc_tt)."""
@@ -2806,24 +2842,16 @@ class _FactorAtt(_FastFunction):
     @staticmethod
     def forward(ctx, qkv, H, W, heads, scale, *wb):
         _chk(qkv, *wb)
+        _att_check('factor_att', qkv, H, W, heads, wb)
         B, N, C3 = qkv.shape
         C = C3 // 3
-        if C * 3 != C3 or H * W != N or C % heads or (C // heads) % 4:
-            raise TcctError(f'factor_att: qkv {tuple(qkv.shape)} does not fit size ({H},{W}) / heads {heads} (Ch must be a multiple of 4)')
-        if sum(w.shape[0] for w in wb[0::2]) != C:
-            raise TcctError('factor_att: the crpe window splits do not add up to the channel count')
         Ch, dt, dev = C // heads, dtype_code(qkv.dtype), qkv.device
         ws = torch.empty(lib.fatt_kstats_workspace_bytes(B, N, C), device=dev, dtype=torch.uint8)
         stats = torch.empty((B, C, 2), device=dev, dtype=torch.float32)
         lib.fatt_kstats(qkv, ws, stats, B, N, C, heads, dt)
         M = ZERO.get((B, heads, Ch, Ch), torch.float32, dev)
         lib.fatt_ktv(qkv, stats, M, B, N, C, heads, dt)
-        cv = torch.empty((B, N, C), device=dev, dtype=qkv.dtype)
-        off = 0
-        for w, b in zip(wb[0::2], wb[1::2]):
-            Cg, K = w.shape[0], w.shape[2]
-            lib.dwk_strided_fwd(qkv[0, 0, 2 * C + off:], 3 * C, w, b, cv[0, 0, off:], C, B, H, W, Cg, K, 0, 0, dt)
-            off += Cg
+        cv = _crpe_forward(qkv, H, W, wb)
         out = torch.empty((B, N, C), device=dev, dtype=qkv.dtype)
         lib.fatt_apply_fwd(qkv, M, cv, out, float(scale), B, N, C, heads, dt)
         ctx.save_for_backward(qkv, stats, M, cv, *wb[0::2])
@@ -2835,7 +2863,6 @@ class _FactorAtt(_FastFunction):
     def backward(ctx, dout):
         qkv, stats, M, cv, *ws = ctx.saved_tensors
         H, W, heads, scale = ctx.cfg
-        wb = ctx.params
         B, N, C3 = qkv.shape
         C = C3 // 3
         dt, dev = dtype_code(qkv.dtype), qkv.device
@@ -2845,24 +2872,12 @@ class _FactorAtt(_FastFunction):
         dqkv = torch.empty_like(qkv)
         dcv = torch.empty_like(cv)
         lib.fatt_apply_bwd(qkv, stats, M, dM, cv, dout, dqkv, dcv, scale, B, N, C, heads, dt)
-        grads, off = [], 0
-        for w, b in zip(wb[0::2], wb[1::2]):
-            Cg, K = w.shape[0], w.shape[2]
-            lib.dwk_strided_fwd(dcv[0, 0, off:], C, w, None, dqkv[0, 0, 2 * C + off:], 3 * C, B, H, W, Cg, K, 1, 1, dt)
-            dw = _grad_out(w)
-            db = _grad_out(b) if b is not None else None
-            lib.dwk_strided_wgrad(qkv[0, 0, 2 * C + off:], 3 * C, dcv[0, 0, off:], C, dw, db, B, H, W, Cg, K, dt)
-            grads += [_ret(dw, w), _ret(db, b)]
-            off += Cg
-        return (dqkv, None, None, None, None) + tuple(grads)
+        return (dqkv, None, None, None, None) + _crpe_backward(qkv, dcv, dqkv, H, W, ctx.params)
 
 
 def factor_att(qkv, size, heads, scale, crpe_convs):
     """qkv [B,N,3C] tokens, size = (H, W), crpe_convs = the nn.Conv2d list of ConvRelPosEnc (windows 3/5/7 over head splits)"""
-    wb = []
-    for m in crpe_convs:
-        wb += [m.weight, m.bias]
-    return _FactorAtt.apply(qkv, int(size[0]), int(size[1]), int(heads), float(scale), *wb)
+    return _FactorAtt.apply(qkv, int(size[0]), int(size[1]), int(heads), float(scale), *_crpe_wb(crpe_convs))
 
 
 class _HydraAtt(_FastFunction):
@@ -2872,22 +2887,14 @@ class _HydraAtt(_FastFunction):
     @staticmethod
     def forward(ctx, qkv, H, W, heads, scale, *wb):
         _chk(qkv, *wb)
+        _att_check('hydra_att', qkv, H, W, heads, wb)
         B, N, C3 = qkv.shape
         C = C3 // 3
-        if C * 3 != C3 or H * W != N or C % heads or (C // heads) % 4:
-            raise TcctError(f'hydra_att: qkv {tuple(qkv.shape)} does not fit size ({H},{W}) / heads {heads} (Ch must be a multiple of 4)')
-        if sum(w.shape[0] for w in wb[0::2]) != C:
-            raise TcctError('hydra_att: the crpe window splits do not add up to the channel count')
         dt, dev = dtype_code(qkv.dtype), qkv.device
         ws = torch.empty(lib.hydra_kv_workspace_bytes(B, N, C), device=dev, dtype=torch.uint8)
         kv = torch.empty((B, C), device=dev, dtype=torch.float32)
         lib.hydra_kv(qkv, ws, kv, B, N, C, heads, dt)
-        cv = torch.empty((B, N, C), device=dev, dtype=qkv.dtype)
-        off = 0
-        for w, b in zip(wb[0::2], wb[1::2]):
-            Cg, K = w.shape[0], w.shape[2]
-            lib.dwk_strided_fwd(qkv[0, 0, 2 * C + off:], 3 * C, w, b, cv[0, 0, off:], C, B, H, W, Cg, K, 0, 0, dt)
-            off += Cg
+        cv = _crpe_forward(qkv, H, W, wb)
         out = torch.empty((B, N, C), device=dev, dtype=qkv.dtype)
         lib.hydra_apply_fwd(qkv, kv, cv, out, float(scale), B, N, C, heads, dt)
         # (under no_grad autograd records no node: the context and what it holds are dropped when apply() returns)
@@ -2900,7 +2907,6 @@ class _HydraAtt(_FastFunction):
     def backward(ctx, dout):
         qkv, kv, cv, *ws = ctx.saved_tensors
         H, W, heads, scale = ctx.cfg
-        wb = ctx.params
         B, N, C3 = qkv.shape
         C = C3 // 3
         dt, dev = dtype_code(qkv.dtype), qkv.device
@@ -2911,84 +2917,52 @@ class _HydraAtt(_FastFunction):
         dqkv = torch.empty_like(qkv)
         dcv = torch.empty_like(cv)
         lib.hydra_apply_bwd(qkv, kv, dkv, cv, dout, dqkv, dcv, scale, B, N, C, heads, dt)
-        grads, off = [], 0
-        for w, b in zip(wb[0::2], wb[1::2]):
-            Cg, K = w.shape[0], w.shape[2]
-            lib.dwk_strided_fwd(dcv[0, 0, off:], C, w, None, dqkv[0, 0, 2 * C + off:], 3 * C, B, H, W, Cg, K, 1, 1, dt)
-            dw = _grad_out(w)
-            db = _grad_out(b) if b is not None else None
-            lib.dwk_strided_wgrad(qkv[0, 0, 2 * C + off:], 3 * C, dcv[0, 0, off:], C, dw, db, B, H, W, Cg, K, dt)
-            grads += [_ret(dw, w), _ret(db, b)]
-            off += Cg
-        return (dqkv, None, None, None, None) + tuple(grads)
+        return (dqkv, None, None, None, None) + _crpe_backward(qkv, dcv, dqkv, H, W, ctx.params)
 
 
 def hydra_att(qkv, size, heads, scale, crpe_convs):
     """qkv [B,N,3C] tokens, size = (H, W), crpe_convs = the nn.Conv2d list of ConvRelPosEnc (windows 3/5/7 over head splits)"""
-    wb = []
-    for m in crpe_convs:
-        wb += [m.weight, m.bias]
-    return _HydraAtt.apply(qkv, int(size[0]), int(size[1]), int(heads), float(scale), *wb)
+    return _HydraAtt.apply(qkv, int(size[0]), int(size[1]), int(heads), float(scale), *_crpe_wb(crpe_convs))
 
 
 class _MaxPool2(_FastFunction):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, fork=False):
+        """fork: also return an alias of x, which is what the OTHER consumers of x read, so that in the backward pass their gradient arrives here and is
+        added inside the pooling scatter kernel (tcct_maxpool2_bwd_add; autograd would otherwise run an accumulation pass)"""
+        if fork:
+            ctx.set_materialize_grads(False)      # an unused output must arrive as None in backward(), not as a zero-filled tensor
         _chk(x)
         N, H, W, C = x.shape
         y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=x.dtype)
         lib.maxpool2_fwd(x, y, N, H, W, C, dtype_code(x.dtype))
         ctx.save_for_backward(x)
-        return y
+        return (y, x.view_as(x)) if fork else y
 
     @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        dy = _as(dy, x.dtype)
-        N, H, W, C = x.shape
-        dx = torch.empty_like(x)
-        lib.maxpool2_bwd(x, dy, dx, N, H, W, C, dtype_code(x.dtype))
-        return dx
-
-
-class _MaxPool2Fork(_FastFunction):
-    """(maxpool2(x), x): the second output aliases x and is what the OTHER consumers of x read, so that in the backward pass their
-    gradient arrives here and is added inside the pooling scatter kernel (autograd would otherwise run an accumulation pass)"""
-
-    @staticmethod
-    def forward(ctx, x):
-        ctx.set_materialize_grads(False)      # an unused output must arrive as None in backward(), not as a zero-filled tensor
-        _chk(x)
-        N, H, W, C = x.shape
-        y = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=x.dtype)
-        lib.maxpool2_fwd(x, y, N, H, W, C, dtype_code(x.dtype))
-        ctx.save_for_backward(x)
-        return y, x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, dy, dskip):
+    def backward(ctx, dy, dskip=None):
         (x,) = ctx.saved_tensors
         N, H, W, C = x.shape
         if dy is None:
-            return dskip
+            return dskip, None
         dy = _as(dy, x.dtype)
         dx = torch.empty_like(x)
         if dskip is None:
             lib.maxpool2_bwd(x, dy, dx, N, H, W, C, dtype_code(x.dtype))
         else:
             lib.maxpool2_bwd_add(x, dy, _as(dskip, x.dtype), dx, N, H, W, C, dtype_code(x.dtype))
-        return dx
+        return dx, None
 
 
 def maxpool2(x):
-    return _MaxPool2.apply(x)
+    return _MaxPool2.apply(x, False)
 
 
 def maxpool2_fork(x):
-    """(maxpool2(x), x'): use x' (an alias of x) for every other consumer of x; see _MaxPool2Fork"""
+    """(maxpool2(x), x'): use x' (an alias of x) for every other consumer of x; see _MaxPool2.forward `fork`"""
     if not (torch.is_grad_enabled() and x.requires_grad):
-        return _MaxPool2.apply(x), x
-    return _MaxPool2Fork.apply(x)
+        return maxpool2(x), x
+    return _MaxPool2.apply(x, True)
 
 
 class _Bilinear(_FastFunction):

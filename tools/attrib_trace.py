@@ -80,6 +80,7 @@ def main():
     wrap_method(T.MPViT, 'iter_stages', gen=True)
     wrap_method(T.Conv2d_BN, 'forward_deferred')
     wrap_method(T.MPUpBlock, 'forward_through')
+    wrap_method(T.MPUpBlock, 'forward_through_aux')
     wrap_method(T.ResBlock, 'tail')
     direction = ['fwd']
     import tcct_amd.nets.reg as R

@@ -304,7 +304,8 @@ def record_steps(arms=None):
             args = parse_args(argv + ['--bs=2', '--db=synth', '--pl=false', f'--root={root}'])
             dtype = args.dtype
             ds = SynthOCT(height=64, width=64, device='cuda')
-            net = nets.stc_tt(ds.out_channels, compute_dtype=BF if dtype == 'bf16' else F32, **(dict(legacy_heads=True) if args.legacy_heads else {}))
+            net = nets.stc_tt(ds.out_channels, compute_dtype=BF if dtype == 'bf16' else F32, **(dict(legacy_heads=True) if args.legacy_heads else {}),
+                              **(dict(att=args.att) if args.att != 'pool' else {}))
             net = nets.RegNet(net, con=args.type_udh, out_channels=ds.out_channels)
             k = KiteSeg(model=net, dataset=ds, root=args.root, args=args)
             k.model.train()
