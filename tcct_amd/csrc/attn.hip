@@ -13,6 +13,7 @@
 #include "common.h"
 
 #define FA_TR 32            // token rows staged per tile of k_fatt_ktv
+#define FA_KTV_MAX_LDS (264 * 256)      // dynamic LDS of k_fatt_ktv at C = 256: 4 (2 FA_TR C + 2 C) bytes
 
 // ------------------------------------------------------------------ softmax statistics of k over the tokens
 // part [B,S,C,2] = (max, sum exp(k - max)) of segment s; element (b,n,c) of k at k[(b*N+n)*ld + c]
@@ -419,6 +420,7 @@ extern "C" int tcct_fatt_kstats(const void* qkv, void* workspace, float* stats, 
 static int ktv_launch(const char* who, const void* A, int64_t lda, const void* Bm, int64_t ldb, const float* stats, float* out, float alpha,
                       int B, int64_t N, int C, int heads, int dtype, hipStream_t st) {
     if (fatt_shape_ok(who, B, N, C, heads)) return -1;
+    TCCT_CHECK(dtype == TCCT_F32 || dtype == TCCT_BF16, "%s: bad dtype %d", who, dtype);       // before the zero fill: a refused call writes nothing
     const int Ch = C / heads;
     if (!tcct_skip_zero_fill() && hipMemsetAsync(out, 0, sizeof(float) * (size_t)B * C * Ch, st) != hipSuccess) {
         tcct_set_error("%s: memset failed", who); return -2;
@@ -426,8 +428,9 @@ static int ktv_launch(const char* who, const void* A, int64_t lda, const void* B
     const int ntiles = (int)((N + FA_TR - 1) / FA_TR);
     const int gx = ntiles < 128 ? ntiles : 128;
     const size_t lds = sizeof(float) * (2 * FA_TR * C + 2 * C);
-    if (stats) { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_fatt_ktv<T, T, true>), dim3(gx, B), dim3(256), lds, st, (const T*)A, lda, (const T*)Bm, ldb, stats, out, alpha, (int)N, C, Ch)); }
-    else { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_fatt_ktv<T, T, false>), dim3(gx, B), dim3(256), lds, st, (const T*)A, lda, (const T*)Bm, ldb, stats, out, alpha, (int)N, C, Ch)); }
+    // 264 C bytes: above the default 64 KB of dynamic LDS from C = 252 on, and fatt_shape_ok accepts C <= 256 -- hence tcct_launch with the bytes of C = 256
+    if (stats) { TCCT_DISPATCH(dtype, tcct_launch<k_fatt_ktv<T, T, true>, FA_KTV_MAX_LDS>(dim3(gx, B), dim3(256), lds, st, (const T*)A, lda, (const T*)Bm, ldb, stats, out, alpha, (int)N, C, Ch)); }
+    else { TCCT_DISPATCH(dtype, tcct_launch<k_fatt_ktv<T, T, false>, FA_KTV_MAX_LDS>(dim3(gx, B), dim3(256), lds, st, (const T*)A, lda, (const T*)Bm, ldb, stats, out, alpha, (int)N, C, Ch)); }
     TCCT_LAUNCH_OK();
 }
 /* M[b,h,k,v] = sum_n softmax_N(k)[b,n,h,k] * v[b,n,h,v]  (fp32 [B,heads,Ch,Ch]) */
