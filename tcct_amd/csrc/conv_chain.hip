@@ -16,18 +16,13 @@
 //
 // Arithmetic: every pixel of either convolution sums bias, then its taps in (dy, dx, half) order on v_mfma_f32_32x32x16_bf16, and the intermediate is
 // rounded to bf16 exactly where the two-launch path stores it => results BIT-IDENTICAL to tcct_conv32_fwd twice (tests/test_kernels_gpu.py).
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 ch_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float ch_f32x16;
+#include "row_stream.h"
 
 #define CH_T 256
-#define CH_R 9                  // producer ring rows (a multiple of 3: ring slot and accumulator index are compile-time in the 9-fold unrolled body)
-#define CH_P 7                  // input rows in flight per producer
-#define CH_ROWB 2176            // 34 pixels x 64 B (input ring rows and mid ring rows alike)
-#define CH_MR 3                 // mid ring rows per strip
 #define CH_SW 30                // output pixels per strip
-#define CH_OOB 0x80000000u
+// CH_R producer ring rows (a multiple of 3: ring slot and accumulator index are compile-time in the 9-fold unrolled body), CH_P input rows in flight per producer,
+// CH_ROWB = 34 pixels x 64 B (input ring rows and mid ring rows alike), CH_MR mid ring rows per strip: row_stream_plan.h
+static_assert(rs_ring_ok(CH_R, CH_P, 3) && CH_R % CH_MR == 0 && ch_lds().bytes <= RS_LDS_2PER_CU, "k_conv32_chain33: ring invariant / LDS cap");
 
 // LDS writes of this wave have landed, then the block barrier: the hand-over of a mid row.  (__syncthreads() would also drain vmcnt -- the DMA pipeline.)
 __device__ __forceinline__ void ch_row_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -44,24 +39,20 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
     const int r = lane & 31, hh = lane >> 5;
     const bool producer = wave < 2;
     const int sidx = wave & 1;                                  // strip of the pair
-    // LDS: [2 producers][CH_R rows] input rings | [2 strips][CH_MR rows] mid rings | [2 consumers] 2 KB transpose scratch | bias1[32] bias2[32] | stats partials [2][64]
+    constexpr ChLds LD = ch_lds();
     unsigned char* ring = smem + sidx * (CH_R * CH_ROWB);
-    unsigned char* midr = smem + 2 * CH_R * CH_ROWB + sidx * (CH_MR * CH_ROWB);
-    unsigned char* scr = smem + 2 * CH_R * CH_ROWB + 2 * CH_MR * CH_ROWB + sidx * 2048;
-    float* sB = reinterpret_cast<float*>(smem + 2 * CH_R * CH_ROWB + 2 * CH_MR * CH_ROWB + 2 * 2048);
-    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
-    const bf16* wp = producer ? wp1 : wp2;
-    ch_bf16x8 Wf[9][2];         // A operands: row co = r, input channels 8 hh + 16 half ..+7 of tap t
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc) Wf[t][kc] = *reinterpret_cast<const ch_bf16x8*>(wp + (t * 32 + r) * 32 + (hh + 2 * kc) * 8);
+    unsigned char* midr = smem + LD.mid + sidx * (CH_MR * CH_ROWB);
+    unsigned char* scr = smem + LD.scr + sidx * 2048;
+    float* sB = reinterpret_cast<float*>(smem + LD.bias);
+    const uint32_t ring_lds = rs_ring_lds(ring);
+    bf16x8 Wf[9][2];
+    rs_load_wfrag<9>(Wf, producer ? wp1 : wp2, r, hh);
     if (tid < 32) sB[tid] = bias1 ? bias1[tid] : 0.f;
     else if (tid < 64) sB[tid] = bias2 ? bias2[tid - 32] : 0.f;
     // mid pixels 32, 33 are never written by the producer and only feed the two output columns nobody stores: give them a defined value once
     if (tid < 2 * CH_MR * 8) {
         const int st = tid / (CH_MR * 8), rem = tid - st * (CH_MR * 8), row = rem >> 3, q = rem & 7;
-        *reinterpret_cast<uint4*>(smem + 2 * CH_R * CH_ROWB + st * (CH_MR * CH_ROWB) + row * CH_ROWB + 2048 + q * 16) = make_uint4(0u, 0u, 0u, 0u);
+        *reinterpret_cast<uint4*>(smem + LD.mid + st * (CH_MR * CH_ROWB) + row * CH_ROWB + 2048 + q * 16) = make_uint4(0u, 0u, 0u, 0u);
     }
     __syncthreads();
     const float* bq = sB + (producer ? 0 : 32);
@@ -70,19 +61,16 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
 #pragma unroll
     for (int d = 0; d < 3; ++d)
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) { const int P = r + d; xB[d][kc] = src + P * 64 + (((hh + 2 * kc) ^ ((P >> 2) & 3)) << 4); }
+        for (int kc = 0; kc < 2; ++kc) xB[d][kc] = src + rs_frag_off64(r + d, hh + 2 * kc);
     constexpr bool ST = MODE == 2;
     float ss[ST ? 8 : 1], sq[ST ? 8 : 1];
 #pragma unroll
     for (int k = 0; k < (ST ? 8 : 1); ++k) ss[k] = sq[k] = 0.f;
-    const int pairs = (strips + 1) >> 1;
-    // consecutive blocks take the strip pairs of ONE run of image rows (whole image rows in flight together), then the next run, then the next image
-    const int q_ = blockIdx.x / pairs, pair = blockIdx.x - q_ * pairs;
-    const int n = q_ / rpi, r0 = (q_ - n * rpi) * run;
-    const int L = __builtin_amdgcn_readfirstlane(H - r0 < run ? H - r0 : run);      // output rows r0 .. r0 + L - 1
-    const int s = 2 * pair + sidx;
-    const bool live = s < strips;
-    const int w0 = s * CH_SW;
+    const RsBlockSeg seg = rs_block_segment(blockIdx.x, (strips + 1) >> 1, rpi, run, H);          // strip groups = the strip pairs; output rows r0 .. r0 + L - 1
+    const int n = seg.n, r0 = seg.r0, L = seg.L;
+    const int s = 2 * seg.grp + sidx;
+    const bool live = s < strips;               // an idle strip runs along with every offset out of range: its waves are partners in the row barriers
+    const int w0 = s * CH_SW, Wl = live ? W : 0;
     const uint32_t img_bytes = (uint32_t)H * (uint32_t)W * 64u;
     const uint32_t rowb = (uint32_t)W * 64u;
     const int groups = (L + 4 + CH_R - 1) / CH_R;               // iterations t = 0 .. L + 3 (see below), whole groups of CH_R
@@ -92,20 +80,13 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
         // iteration t: input halo row t (image row r0 - 2 + t) arrives; mid row m = t - 2 (image row r0 - 1 + m, m = 0 .. L + 1) is complete after its MFMAs
         const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
         const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(mid + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
-        const int pq = lane >> 2, cs = (lane & 3) ^ ((lane >> 4) & 3);          // LDS position lane & 3 of ring pixel 16 piece + pq holds chunk cs
-        const int c0 = w0 - 2 + pq, c1 = w0 + 14 + pq, c2 = w0 + 30 + pq;
-        const uint32_t o0 = (live && c0 >= 0 && c0 < W) ? (uint32_t)(c0 * 64 + cs * 16) : CH_OOB;
-        const uint32_t o1 = (live && c1 < W) ? (uint32_t)(c1 * 64 + cs * 16) : CH_OOB;
-        const uint32_t o2 = (live && c2 < W) ? (uint32_t)(c2 * 64 + cs * 16) : CH_OOB;
-        // the 30 mid pixels this strip owns (mid pixel 1 + i <-> image column w0 + i), 16-byte pieces: piece 64 u + lane -> pixel 16 u + (lane >> 2)
+        const int c0 = w0 - 2 + p16, cs16 = rs_dma_chunk(lane) * 16;
+        const uint32_t o0 = rs_col_off(c0, Wl, 64, cs16), o1 = rs_col_off(c0 + 16, Wl, 64, cs16), o2 = rs_col_off(c0 + 32, Wl, 64, cs16);
+        // the 30 mid pixels this strip owns (mid pixel 1 + i <-> image column w0 + i) leave from the mid ring slot itself: sl = where rs_store_offs' pieces sit in it
         uint32_t so[2], sl[2];
+        rs_store_offs(so, w0, Wl, 64, cch * 16, lane, CH_SW);
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int i = 16 * u + p16, wo = w0 + i;
-            so[u] = (live && i < CH_SW && wo < W) ? (uint32_t)(wo * 64 + cch * 16) : CH_OOB;
-            const int P = 1 + i;
-            sl[u] = (uint32_t)(P * 64 + ((cch ^ ((P >> 2) & 3)) << 4));
-        }
+        for (int u = 0; u < 2; ++u) sl[u] = rs_frag_off64(1 + 16 * u + p16, cch);
         const int mcol = w0 - 1 + r;                            // image column of this lane's mid pixel
         const bool colin = live && mcol >= 0 && mcol < W;
         const uint32_t mw = (uint32_t)(r * 64 + hh * 8);        // + ((q ^ swz) << 4): this lane's four 8-byte pieces of mid pixel r
@@ -116,36 +97,30 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
             const bool xin = a <= L + 3 && ri >= 0 && ri < H;
             const uint32_t ro = (uint32_t)(xin ? ri : 0) * rowb;
             const uint32_t base = ring_lds + (uint32_t)(slot * CH_ROWB);
-            lds_dma16(rx, xin ? o0 + ro : CH_OOB, base);
-            lds_dma16(rx, xin ? o1 + ro : CH_OOB, base + 1024u);
-            if (lane < 8) lds_dma16(rx, xin ? o2 + ro : CH_OOB, base + 2048u);
+            lds_dma16(rx, xin ? o0 + ro : OOB_OFF, base);
+            lds_dma16(rx, xin ? o1 + ro : OOB_OFF, base + 1024u);
+            if (lane < 8) lds_dma16(rx, xin ? o2 + ro : OOB_OFF, base + 2048u);
         };
 #pragma unroll
         for (int a = 0; a < CH_P; ++a) issue(a, a);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (CH_P - 1)) : "memory");
-        ch_bf16x8 X[3][2], Xn[3][2];
+        rs_wait_row<3, CH_P>();
+        bf16x8 X[3][2], Xn[3][2];
 #pragma unroll
         for (int d = 0; d < 3; ++d)
 #pragma unroll
-            for (int kc = 0; kc < 2; ++kc) X[d][kc] = *reinterpret_cast<const ch_bf16x8*>(xB[d][kc]);
-        ch_f32x16 acc[3];
+            for (int kc = 0; kc < 2; ++kc) X[d][kc] = *reinterpret_cast<const bf16x8*>(xB[d][kc]);
+        f32x16 acc[3];
         for (int g = 0; g < groups; ++g) {
 #pragma unroll
             for (int j = 0; j < CH_R; ++j) {
                 const int t = g * CH_R + j;
                 issue(t + CH_P, (j + CH_P) % CH_R);
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (CH_P - 1)) : "memory");          // halo row t + 1 has landed (loads retire in order among loads)
+                rs_wait_row<3, CH_P>();                 // halo row t + 1 has landed
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
 #pragma unroll
-                    for (int kc = 0; kc < 2; ++kc) Xn[d][kc] = *reinterpret_cast<const ch_bf16x8*>(xB[d][kc] + ((j + 1) % CH_R) * CH_ROWB);
-                {           // mid row t starts at the bias of this lane's 16 channels
-                    float4 b4[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) b4[q] = *reinterpret_cast<const float4*>(bq + 8 * q + 4 * hh);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { acc[j % 3][4 * q] = b4[q].x; acc[j % 3][4 * q + 1] = b4[q].y; acc[j % 3][4 * q + 2] = b4[q].z; acc[j % 3][4 * q + 3] = b4[q].w; }
-                }
+                    for (int kc = 0; kc < 2; ++kc) Xn[d][kc] = *reinterpret_cast<const bf16x8*>(xB[d][kc] + ((j + 1) % CH_R) * CH_ROWB);
+                rs_acc_bias(acc[j % 3], bq, hh);        // mid row t starts
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy)          // halo row t is tap row dy of mid row t - dy
@@ -159,7 +134,7 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
                 const int m = t - 2;
                 const int64_t mrow = (int64_t)r0 - 1 + m;
                 const bool rowin = m >= 0 && m <= L + 1 && mrow >= 0 && mrow < H;
-                const ch_f32x16& A = acc[(j + 1) % 3];
+                const f32x16& A = acc[(j + 1) % 3];
                 unsigned char* slot = midr + ((j + 1) % CH_MR) * CH_ROWB;           // (t - 2) mod 3 == (j + 1) mod 3 because CH_R is a multiple of 3
                 const bool keep = rowin && colin;
 #pragma unroll
@@ -178,7 +153,7 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
                 const uint32_t oro = (uint32_t)(own ? mrow : 0) * rowb;
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
-                    __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, (own && so[u] != CH_OOB) ? so[u] + oro : CH_OOB, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, (own && so[u] != OOB_OFF) ? so[u] + oro : OOB_OFF, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
@@ -186,22 +161,17 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
                     for (int kc = 0; kc < 2; ++kc) X[d][kc] = Xn[d][kc];
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        rs_wait_all();
     } else {
         // ---------------------------------------------------------------------------------------------- convolution 2
         // iteration t: after B_t mid row m = t - 2 (halo row m of this convolution) is in the ring; output row o = m - 2 = t - 4 (image row r0 + o) is complete after it
         const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE == 3 ? res : y) + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
         uint32_t so[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int i = 16 * u + p16, wo = w0 + i;
-            so[u] = (live && i < CH_SW && wo < W) ? (uint32_t)(wo * 64 + cch * 16) : CH_OOB;
-        }
-        const int ocol = w0 + r;
-        const uint32_t radd = (live && r < CH_SW && ocol < W) ? (uint32_t)(ocol * 64 + hh * 8) : CH_OOB;         // + 16 q: this lane's channels 8 q + 4 hh ..+3 of `res`
-        ch_f32x16 acc[3];
-        ch_bf16x8 X[3][2];
+        rs_store_offs(so, w0, Wl, 64, cch * 16, lane, CH_SW);
+        const uint32_t radd = r < CH_SW ? rs_col_off(w0 + r, Wl, 64, hh * 8) : OOB_OFF;         // + 16 q: this lane's channels 8 q + 4 hh ..+3 of `res`
+        f32x16 acc[3];
+        bf16x8 X[3][2];
         for (int g = 0; g < groups; ++g) {
 #pragma unroll
             for (int j = 0; j < CH_R; ++j) {
@@ -213,7 +183,7 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
                     const uint32_t oro = (uint32_t)(ovalid ? r0 + o : 0) * rowb;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rr, (ovalid && radd != CH_OOB) ? radd + oro + 16u * q : CH_OOB, 0, 0);
+                        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rr, (ovalid && radd != OOB_OFF) ? radd + oro + 16u * q : OOB_OFF, 0, 0);
                         rv[q].x = v[0]; rv[q].y = v[1];
                     }
                 }
@@ -221,14 +191,8 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
 #pragma unroll
-                    for (int kc = 0; kc < 2; ++kc) X[d][kc] = *reinterpret_cast<const ch_bf16x8*>(xB[d][kc] + ((j + 1) % CH_MR) * CH_ROWB);
-                {           // output row t - 2 starts at the bias (its first tap row is this halo row)
-                    float4 b4[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) b4[q] = *reinterpret_cast<const float4*>(bq + 8 * q + 4 * hh);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { acc[(j + 1) % 3][4 * q] = b4[q].x; acc[(j + 1) % 3][4 * q + 1] = b4[q].y; acc[(j + 1) % 3][4 * q + 2] = b4[q].z; acc[(j + 1) % 3][4 * q + 3] = b4[q].w; }
-                }
+                    for (int kc = 0; kc < 2; ++kc) X[d][kc] = *reinterpret_cast<const bf16x8*>(xB[d][kc] + ((j + 1) % CH_MR) * CH_ROWB);
+                rs_acc_bias(acc[(j + 1) % 3], bq, hh);  // output row t - 2 starts (its first tap row is this halo row)
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy)          // mid row m = t - 2 is tap row dy of output row m - dy; accumulator of output row o' lives at (o' + 3) % 3 ... (j + 1 - dy) % 3
@@ -239,7 +203,7 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
                             acc[(j + 4 - dy) % 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[dy * 3 + d][kc], X[d][kc], acc[(j + 4 - dy) % 3], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 // output row o = t - 4 is complete (accumulator (j + 2) % 3): (+ res), pack, transpose through this wave's scratch, store 30 pixels
-                ch_f32x16& A = acc[(j + 2) % 3];
+                f32x16& A = acc[(j + 2) % 3];
                 uint2 ov[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -250,52 +214,26 @@ k_conv32_chain33(const bf16* __restrict__ x, const bf16* __restrict__ wp1, const
                     }
                     ov[q].x = pack_bf16x2(v4[0], v4[1]); ov[q].y = pack_bf16x2(v4[2], v4[3]);
                 }
-                const int f = (r >> 1) & 3;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(scr + r * 64 + ((q ^ f) << 4) + hh * 8) = ov[q];
-                wave_lds_fence();
                 u32x4 pend[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(scr + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
-                wave_lds_fence();
+                rs_transpose_row(scr, ov, pend, lane);
                 const uint32_t oro = (uint32_t)(ovalid ? r0 + o : 0) * rowb;
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    const bool inb = ovalid && so[u] != CH_OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, inb ? so[u] + oro : CH_OOB, 0, 0);
-                    if (ST) {
-                        if (inb) {
-                            const uint32_t wv[4] = {pend[u][0], pend[u][1], pend[u][2], pend[u][3]};
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                float u0 = __uint_as_float(wv[k] << 16), u1 = __uint_as_float(wv[k] & 0xffff0000u);
-                                u0 = fmaxf(u0, 0.01f * u0); u1 = fmaxf(u1, 0.01f * u1);
-                                ss[2 * k] += u0; sq[2 * k] += u0 * u0; ss[2 * k + 1] += u1; sq[2 * k + 1] += u1 * u1;
-                            }
-                        }
+                    const bool inb = ovalid && so[u] != OOB_OFF;
+                    __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, inb ? so[u] + oro : OOB_OFF, 0, 0);
+                    if constexpr (ST) {
+                        if (inb) rs_stats_add<true>(ss, sq, pend[u]);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     }
-    if (ST) {
-        // a consumer lane owns channels 8 (lane & 3) ..+7 of the pixels it stored: butterfly over lane bits 2..5, per-wave LDS slots, fp64 atomics
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (ST) {
+        rs_wait_all();
         __syncthreads();
-        float* red = sB + 64;
-        if (!producer) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                float a = ss[k], b = sq[k];
-#pragma unroll
-                for (int o = 32; o > 2; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-                if (lane < 4) {
-                    red[sidx * 64 + 8 * lane + k] = a;
-                    red[sidx * 64 + 32 + 8 * lane + k] = b;
-                }
-            }
-        }
+        float* red = reinterpret_cast<float*>(smem + LD.part);          // the two consumers' slots, fp64 atomics
+        if (!producer) rs_stats_fold(ss, sq, red + sidx * 64, lane);
         __syncthreads();
         if (tid < 64) atomicAdd(&stats[tid], (double)red[tid] + (double)red[64 + tid]);
     }
@@ -312,22 +250,15 @@ extern "C" int tcct_conv32_chain33(const void* x, const void* wp1, const float* 
     TCCT_CHECK(x && wp1 && wp2 && y && x != mid && mid != y && x != y, "conv32_chain33: x, mid, y must be three tensors (mid may be NULL)");
     TCCT_CHECK(!(stats && res), "conv32_chain33: statistics and a residual exclude each other");
     TCCT_CHECK(N > 0 && H > 0 && W > 0 && (int64_t)H * W * 64 < (1LL << 31), "conv32_chain33: one image of %d x %d exceeds the 2 GiB buffer-descriptor range", H, W);
-    const int strips = (W + CH_SW - 1) / CH_SW, pairs = (strips + 1) / 2;
+    const int strips = (W + CH_SW - 1) / CH_SW;
     // runs per image: as many as fill the 512 block slots; a run pays 4 extra input rows + the pipeline fill, so >= 24 rows on the large maps, >= 8 on the
     // small ones (where the block count matters more than the fill)
-    const int minrun = H >= 96 ? 24 : 8;
-    int rpi = 512 / (N * pairs);
-    if (rpi > H / minrun) rpi = H / minrun;
-    if (rpi < 1) rpi = 1;
-    const int run = (H + rpi - 1) / rpi;
-    rpi = (H + run - 1) / run;
-    const int64_t blocks = (int64_t)N * rpi * pairs;
-    TCCT_CHECK(blocks < (1LL << 31), "conv32_chain33: too many blocks");
-    const size_t lds = (size_t)2 * CH_R * CH_ROWB + (size_t)2 * CH_MR * CH_ROWB + 2 * 2048 + 64 * 4 + 128 * 4;
+    const RsGridPlan pl = rs_grid_plan(N, H, strips, 2, 512, H >= 96 ? 24 : 8, 0);          // always launched: `taken` is not asked
+    TCCT_CHECK(pl.blocks < (1LL << 31), "conv32_chain33: too many blocks");
     hipStream_t st = (hipStream_t)stream;
 #define CH_LAUNCH(M)                                                                                                                                  \
-    tcct_launch<k_conv32_chain33<M>, 80 * 1024>(dim3((unsigned)blocks), dim3(CH_T), lds, st, (const bf16*)x, (const bf16*)wp1, bias1, (bf16*)mid,     \
-                                                (const bf16*)wp2, bias2, (bf16*)y, (const bf16*)res, N, H, W, strips, run, rpi, stats)
+    tcct_launch<k_conv32_chain33<M>, RS_LDS_2PER_CU>(dim3((unsigned)pl.blocks), dim3(CH_T), ch_lds().bytes, st, (const bf16*)x, (const bf16*)wp1, bias1, (bf16*)mid, \
+                                                     (const bf16*)wp2, bias2, (bf16*)y, (const bf16*)res, N, H, W, strips, pl.run, pl.rpi, stats)
     if (stats) CH_LAUNCH(2);
     else if (res) CH_LAUNCH(3);
     else CH_LAUNCH(0);

@@ -9,13 +9,9 @@
 //   weights use the same image with row = tap*32+co.  HORZ tiles (8 rows x 64 cols, M-tiles along W) serve 3x3 and 1xk;
 //   VERT tiles (64 rows x 8 cols, column-major LDS image, M-tiles along H) serve kx1 with a 1.19x halo instead of 2.5x.
 // Each block stages the packed weights once and walks tiles grid-stride; 2 blocks/CU overlap staging with MFMA.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "row_stream.h"
 
 #define MB 256
-#define OOB_OFF 0x80000000u     // buffer offset beyond every descriptor range used here (< 2 GiB): loads return 0, stores are dropped
 
 // OIHW fp32 -> [tap][co][ci] bf16 (optionally flipped + transposed: the weights of the input-gradient convolution)
 // The 32x32 block (o_off.., i_off..) of an OIHW weight with `ldi` input channels is selected, so 32->64 / 64->32 convolutions
@@ -357,14 +353,14 @@ k_conv32_mfma(const bf16* __restrict__ x, const bf16* __restrict__ wp, const flo
                 const bool inb = ho < H && wo < W;
                 const u32x4 ov = pend[u];
                 __builtin_amdgcn_raw_buffer_store_b128(ov, ws, inb ? (uint32_t)((ho * W + wo) * ys * 2 + cch * 16) : OOB_OFF, 0, 0);
-                if (STATS >= 1 && STATS <= 3) {
+                if constexpr (STATS == 1 || STATS == 2) {
+                    if (inb) rs_stats_add<STATS == 2>(ss, sq, ov);
+                } else if constexpr (STATS == 3) {          // a run-time pre-activation: not the shared form
                     if (inb) {
                         const uint32_t wv[4] = {ov[0], ov[1], ov[2], ov[3]};
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
-                            float u0 = __uint_as_float(wv[k] << 16), u1 = __uint_as_float(wv[k] & 0xffff0000u);
-                            if (STATS == 2) { u0 = fmaxf(u0, 0.01f * u0); u1 = fmaxf(u1, 0.01f * u1); }      // LeakyReLU(u) == max(u, 0.01 u): mul + max instead of mul + cmp + select
-                            else if (STATS == 3) { u0 = act_fwd(stat_pre, u0); u1 = act_fwd(stat_pre, u1); }
+                            const float u0 = act_fwd(stat_pre, __uint_as_float(wv[k] << 16)), u1 = act_fwd(stat_pre, __uint_as_float(wv[k] & 0xffff0000u));
                             ss[2 * k] += u0; sq[2 * k] += u0 * u0; ss[2 * k + 1] += u1; sq[2 * k + 1] += u1 * u1;
                         }
                     }
@@ -392,7 +388,7 @@ k_conv32_mfma(const bf16* __restrict__ x, const bf16* __restrict__ wp, const flo
             for (int h2 = 0; h2 < RND; ++h2) {
                 __builtin_amdgcn_sched_barrier(0);          // pack arithmetic above (behind the previous round's reads), stores below
                 if (t > 0 || h2 > 0) flush(h2 > 0 ? t : t - 1, h2 > 0 ? h2 - 1 : RND - 1);    // the previous round: its reads are long done
-                // one wave writes and reads its own scratch: LDS operations of a wave complete in order (the fences are for the compiler)
+                // one wave writes and reads its own scratch (rs_transpose_row is the WIDE form of this; the narrow form writes one half of the M-tile per round)
                 if (WIDE) {
                     const int f = (r >> 1) & 3;
 #pragma unroll
@@ -414,21 +410,10 @@ k_conv32_mfma(const bf16* __restrict__ x, const bf16* __restrict__ wp, const flo
         flush(3, RND - 1);
         __syncthreads();                                    // the staged image of the next tile is complete
     }
-    if (STATS >= 1 && STATS <= 3) {
-        // lanes with equal (lane & 3) hold different pixels of the same 8 channels: butterfly over lane bits 2..5, LDS, fp64 atomics
-        // (once per block: LDS float atomics are slow, a per-tile flush of the partials cost +70 % kernel time)
+    if constexpr (STATS >= 1 && STATS <= 3) {          // once per block: rs_stats_fold into [4 waves][64] over the (dead) image, fp64 atomics
         __syncthreads();
-        float* red = reinterpret_cast<float*>(sX);          // [4 waves][64]
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float a = ss[k], b = sq[k];
-#pragma unroll
-            for (int o = 32; o > 2; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-            if (lane < 4) {             // per-wave slots, summed below: no LDS atomics
-                red[wave * 64 + 8 * lane + k] = a;
-                red[wave * 64 + 32 + 8 * lane + k] = b;
-            }
-        }
+        float* red = reinterpret_cast<float*>(sX);
+        rs_stats_fold(ss, sq, red + wave * 64, lane);
         __syncthreads();
         if (tid < 64) atomicAdd(&stats[tid < 32 ? tid : stats_sq_off + tid - 32], (double)red[tid] + (double)red[64 + tid] + (double)red[128 + tid] + (double)red[192 + tid]);
     }
@@ -754,6 +739,7 @@ k_conv32_wgrad(const bf16* __restrict__ x, const bf16* __restrict__ dy, float* _
     // block-level reduction of the WPG = 4/TG partial accumulators per tap in LDS: the waves of a tap group take turns (plain
     // stores / read-add-write, one barrier per turn).  LDS float atomics did this before and cost ~25 us per BLOCK (a one-tile
     // launch took 37 us against 9 us for the forward kernel), i.e. most of the time of every call below level 1.
+    // (Written out, not through rs_wgrad_put: the generic kernel is the comparison arm of the bit-compatibility tests and keeps its code as it was.)
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);
     for (int turn = 0; turn < WPG; ++turn) {
@@ -919,15 +905,7 @@ k_conv32_wgrad33_roll(const bf16* __restrict__ x, const bf16* __restrict__ dy, f
     for (int turn = 0; turn < 2; ++turn) {
         if (wi == turn) {
 #pragma unroll
-            for (int t = 0; t < 3; ++t) {
-                const int tap = t * 3 + g;
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const int co = (k & 3) + 8 * (k >> 2) + 4 * hh;
-                    float* dst = &red[tap * 1024 + co * 32 + r];
-                    *dst = turn == 0 ? acc[t][k] : *dst + acc[t][k];
-                }
-            }
+            for (int t = 0; t < 3; ++t) rs_wgrad_put(red, t * 3 + g, acc[t], turn == 0, r, hh);
         }
         __syncthreads();
     }
@@ -936,7 +914,7 @@ k_conv32_wgrad33_roll(const bf16* __restrict__ x, const bf16* __restrict__ dy, f
         atomicAdd(&dw[(int64_t)cc * 9 + tap], red[tap * 1024 + cc]);
     }
     if (dbias && g == 0) {
-        bsum += __shfl_xor(bsum, 32, 64);
+        bsum = rs_bsum_fold(bsum);
         __syncthreads();
         if (lane < 32) red[wi * 32 + r] = bsum;
     } else __syncthreads();
@@ -949,17 +927,14 @@ k_conv32_wgrad33_roll(const bf16* __restrict__ x, const bf16* __restrict__ dy, f
 // tile set and nothing, and the three forms tie at ~0.23 ms whatever their LDS / instruction budget is.  Here nothing is shared between waves: a wave
 // owns a 16-pixel-wide column strip of one image and walks down its rows.  Row a of the strip (18 x pixels with the two halo columns + 16 dy pixels,
 // 2176 B) travels global -> LDS by three `buffer_load_dwordx4 ... lds` pieces into a wave-private ring of WS_R rows; WS_P rows are always in flight
-// (issued one per row consumed: `s_waitcnt vmcnt(3 (WS_P - 1))` retires exactly the next row), so the memory pipe sees a steady stream instead of tile
+// (issued one per row consumed: rs_wait_row retires exactly the next row), so the memory pipe sees a steady stream instead of tile
 // bursts.  Per row: the three dx operands are three transposing reads of the same LDS row at pixel offsets 0, 1, 2, the dy fragments of rows a, a - 1,
 // a - 2 roll through registers, nine MFMAs into nine accumulators (all taps in one wave: 144 accumulator registers, two waves per SIMD).  No block
 // barrier until the final reduction.  Out-of-image rows / columns and the dy rows behind a segment's end are buffer-range misses (the DMA writes zeros).
 // Work: the strips of all images form one sequence of N * strips * H rows, cut into equal runs of rows per wave (a run may continue into the next strip).
 #define WS_T 256
-#define WS_R 9                  // ring rows per wave (a multiple of 3: ring slot and dy-window position are compile-time in the 9-fold unrolled body)
-#define WS_P 7                  // rows in flight
-#define WS_ROWB 2176            // 18 x pixels (1152 B) + 16 dy pixels (1024 B)
 #define WS_MIN_RUN 32            // rows per wave below which the pipeline fill (7 rows per segment) costs more than the tiles' barriers: levels 0-1 stream, 2-4 roll
-// (lds_dma16 / make_rsrc_words: common.h)
+// WS_R ring rows per wave (a multiple of 3: ring slot and dy-window position are compile-time in the 9-fold unrolled body), WS_P rows in flight: row_stream_plan.h
 // WIDE (dW [64][32][3][3], MPViT stem[1]): the waves form PAIRS on one strip; wave 2 p + o takes the 64-byte half o of dy's 128-byte pixels (output channels 32 o ..+31) against
 // its own ring copy of the SAME x rows -- the pair's DMA addresses coincide in time, so every 128-byte dy line and every x line crosses HBM once, the second reader hits L2 --
 // and the closing reduction keeps one LDS image per slab (2 x 36 KB): still one global atomic per element and block.  dbias [64].
@@ -967,13 +942,14 @@ template <bool WIDE>
 __global__ void __launch_bounds__(WS_T, 2)
 k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, float* __restrict__ dw, float* __restrict__ dbias,
                         int N, int H, int W, int strips, int run) {
+    static_assert(rs_ring_ok(WS_R, WS_P, 3) && WS_T == 64 * RS_WAVES && ws_lds_bytes() <= RS_LDS_2PER_CU && ws_lds_bytes() >= 2 * 9 * 4096,
+                  "k_conv32_wgrad33_stream: ring invariant / LDS cap / the reduction images (two when WIDE) live in the rings");
     constexpr int SL = WIDE ? 2 : 1, NS = WS_T / 64 / SL;        // dy slabs = waves per strip; strips per block
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, hh = lane >> 5;
     const int slab = WIDE ? (wave & 1) : 0, ws_ = WIDE ? (wave >> 1) : wave;
     unsigned char* ring = smem + wave * (WS_R * WS_ROWB);
-    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
+    const uint32_t ring_lds = rs_ring_lds(ring);
     const unsigned char* xb = tr_lane_base(ring, lane);
     f32x16 acc[9];
 #pragma unroll
@@ -990,18 +966,14 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
     const uint32_t rowb = (uint32_t)W * 64u;
     const int px = lane >> 2, c = lane & 3;
     while (cur < end) {
-        const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * NS + ws_;
-        const int left = (int)(end - cur);
-        const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // dy rows r0 .. r0 + L - 1; x rows r0 - 1 .. r0 + L
-        if (s >= strips) { cur += L; continue; }
-        const int w0 = s * 16;
+        const RsSeg seg = rs_run_segment(cur, end, H, sgroups, NS, ws_);
+        const int n = seg.n, r0 = seg.r0, L = seg.L;                // dy rows r0 .. r0 + L - 1; x rows r0 - 1 .. r0 + L
+        if (seg.s >= strips) { cur += L; continue; }
+        const int w0 = seg.s * 16;
         const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
         const u32x4 rd = make_rsrc_words(dy + (int64_t)n * H * W * (32 * SL), img_bytes * SL);
-        const int cx1 = w0 - 1 + px, cx2 = w0 + 15 + px, cd = w0 + px;
-        const uint32_t ox1 = (cx1 >= 0 && cx1 < W) ? (uint32_t)(cx1 * 64 + c * 16) : OOB_OFF;
-        const uint32_t ox2 = (cx2 < W) ? (uint32_t)(cx2 * 64 + c * 16) : OOB_OFF;
-        const uint32_t od = (cd < W) ? (uint32_t)(cd * (64 * SL) + slab * 64 + c * 16) : OOB_OFF;
+        const uint32_t ox1 = rs_col_off(w0 - 1 + px, W, 64, c * 16), ox2 = rs_col_off(w0 + 15 + px, W, 64, c * 16);
+        const uint32_t od = rs_col_off(w0 + px, W, 64 * SL, slab * 64 + c * 16);
         const uint32_t row0 = (uint32_t)(r0 - 1) * rowb;            // r0 = 0: wraps far beyond the descriptor range -> zeros (the padding row)
         // halo row a of the segment -> ring slot `slot`; rows behind the segment (a > L + 1) and dy rows a >= L are all-miss pieces (zeros, no HBM traffic)
         auto issue = [&](int a, int slot) {
@@ -1014,7 +986,7 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
         };
 #pragma unroll
         for (int a = 0; a < WS_P; ++a) issue(a, a);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (WS_P - 1)) : "memory");
+        rs_wait_row<3, WS_P>();
         bf16x8 X[3], D[3], Xn[3], Dn;
 #pragma unroll
         for (int d = 0; d < 3; ++d) X[d] = tr_load8p(xb + d * 64);
@@ -1027,7 +999,7 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
             for (int j = 0; j < WS_R; ++j) {
                 const int a = g * WS_R + j;
                 issue(a + WS_P, (j + WS_P) % WS_R);
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (WS_P - 1)) : "memory");         // row a + 1 has landed
+                rs_wait_row<3, WS_P>();                 // row a + 1 has landed
                 const unsigned char* nx = xb + ((j + 1) % WS_R) * WS_ROWB;
 #pragma unroll
                 for (int d = 0; d < 3; ++d) Xn[d] = tr_load8p(nx + d * 64);
@@ -1045,23 +1017,17 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
                 D[(j + 1) % 3] = Dn;
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the all-miss pieces behind the segment: the next segment reuses their slots
+        rs_wait_all();
         cur += L;
     }
-    // the waves of a block take turns adding their nine 32 x 32 partial sums into one LDS image per dy slab (no LDS float atomics), then one atomic per element
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the waves of a block take turns adding their nine 32 x 32 partial sums into one LDS image per dy slab, then one atomic per element
+    rs_wait_all();
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);
     for (int turn = 0; turn < NS; ++turn) {
         if (ws_ == turn) {
 #pragma unroll
-            for (int t = 0; t < 9; ++t)
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const int co = (k & 3) + 8 * (k >> 2) + 4 * hh;
-                    float* dst = &red[slab * 9216 + t * 1024 + co * 32 + r];
-                    *dst = turn == 0 ? acc[t][k] : *dst + acc[t][k];
-                }
+            for (int t = 0; t < 9; ++t) rs_wgrad_put(red, slab * 9 + t, acc[t], turn == 0, lane & 31, lane >> 5);
         }
         __syncthreads();
     }
@@ -1072,8 +1038,8 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
     }
     __syncthreads();
     if (dbias) {
-        bsum += __shfl_xor(bsum, 32, 64);
-        if (lane < 32) red[wave * 32 + r] = bsum;
+        bsum = rs_bsum_fold(bsum);
+        if (lane < 32) red[wave * 32 + lane] = bsum;
         __syncthreads();
         if (!WIDE && tid < 32) atomicAdd(&dbias[tid], red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid]);
         if (WIDE && tid < 64) atomicAdd(&dbias[tid], red[tid] + red[64 + tid]);         // channel tid = 32 o + c: waves o and o + 2
@@ -1088,15 +1054,9 @@ k_conv32_wgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy,
 // live in registers for the whole kernel (no weight image in LDS), output row a - 2 is complete after the row's MFMAs and leaves through the per-wave
 // transpose (in the ring slot that is free at that moment) as two 1 KB stores.  The DMA pieces put chunk c of ring pixel P at position c ^ ((P >> 2) & 3)
 // (the permutation is applied to the SOURCE offsets): conflict-free ds_read_b128 at any dx on linear 64-byte pixel rows.  Every row issues
-// exactly 3 DMA pieces; `s_waitcnt vmcnt(3 (FS_P - 1))` retires the next row whatever the stores in between do.
+// exactly 3 DMA pieces; rs_wait_row retires the next row whatever the stores in between do.
 #define FS_T 256
-#define FS_R 9
-#define FS_P 7
-#define FS_ROWB 2176            // 34 halo pixels x 64 B
 #define FS_MIN_RUN 24
-#ifndef FS_SYNC
-#define FS_SYNC 1
-#endif
 template <int STATS, bool WIDE = false>            // 0: none; 1: statistics of y; 2: of LeakyReLU(y) (y as stored) -> stats[0..31], stats[stats_sq_off ..+32) (fp64 atomics);
                                 // 4 / 5 / 6: inference epilogue y = post(a[c] * pre(conv + bias) + b[c]) (eval-mode BatchNorm folded in, as k_conv32_mfma<.., 4, ..>) with
                                 // (pre, post) = (none, none) / (none, LeakyReLU) / (LeakyReLU, none) -- compile-time: the run-time switch of affine4(), unrolled 9 x 4
@@ -1110,22 +1070,20 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
                       int N, int H, int W, int strips, int run, int rpi, double* __restrict__ stats, int stats_sq_off,
                       const float* __restrict__ aff, int wps) {
     static_assert(!(WIDE && STATS >= 4), "k_conv32_fwd33_stream: the wide form has no inference epilogue");
+    static_assert(rs_ring_ok(FS_R, FS_P, 3) && FS_T == 64 * RS_WAVES && fs_lds(WIDE).bytes <= RS_LDS_2PER_CU, "k_conv32_fwd33_stream: ring invariant / LDS cap");
     constexpr int SL = WIDE ? 2 : 1, NB = 32 * SL;          // output slabs = waves per strip; bias floats in front of the statistics partials
+    constexpr int nw = RS_WAVES, ns = nw / SL;              // waves per block; adjacent strips per block
+    constexpr FsLds LD = fs_lds(WIDE);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int nw = blockDim.x >> 6;             // waves per block (4)
-    const int ns = nw / SL;                     // adjacent strips per block
     const int slab = WIDE ? (wave & 1) : 0, ws_ = WIDE ? (wave >> 1) : wave;         // output slab and strip-in-block of this wave
     if (WIDE) wp += slab * wps;
     unsigned char* ring = smem + wave * (FS_R * FS_ROWB);
-    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
-    float* sB = reinterpret_cast<float*>(smem + nw * FS_R * FS_ROWB);          // bias[32], then the statistics partials [nw][64]
-    bf16x8 Wf[9][2];            // A operands: row co = r, input channels 8 hh + 16 half ..+7 of tap t
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc) Wf[t][kc] = *reinterpret_cast<const bf16x8*>(wp + (t * 32 + r) * 32 + (hh + 2 * kc) * 8);
+    const uint32_t ring_lds = rs_ring_lds(ring);
+    float* sB = reinterpret_cast<float*>(smem + LD.bias);
+    bf16x8 Wf[9][2];
+    rs_load_wfrag<9>(Wf, wp, r, hh);
     if (tid < NB) sB[tid] = bias ? bias[tid] : 0.f;
     const float* sBl = sB + 32 * slab;          // this wave's 32 biases
     if (STATS >= 4 && tid < 64) sB[32 + tid] = aff ? aff[tid] : (tid < 32 ? 1.f : 0.f);     // a[32], b[32] of the folded BatchNorm (the statistics partials' place)
@@ -1134,48 +1092,30 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
 #pragma unroll
     for (int d = 0; d < 3; ++d)
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) { const int P = r + d; xB[d][kc] = ring + P * 64 + (((hh + 2 * kc) ^ ((P >> 2) & 3)) << 4); }
+        for (int kc = 0; kc < 2; ++kc) xB[d][kc] = ring + rs_frag_off64(r + d, hh + 2 * kc);
     constexpr bool ST = STATS >= 1 && STATS <= 2;
     float ss[ST ? 8 : 1], sq[ST ? 8 : 1];
 #pragma unroll
     for (int k = 0; k < (ST ? 8 : 1); ++k) ss[k] = sq[k] = 0.f;
-    // the waves of a block walk ADJACENT strips over the same rows (nw x 2 KB of every image row between them, at about the same time)
-    const int sgroups = (strips + ns - 1) / ns;
-    // Row-major block order: consecutive blocks take the strip groups of ONE run of image rows, so whole image rows are in flight together (0.1838 ms at
-    // level 0 against 0.1893 for runs cut from the strip-major sequence of rows).  rpi = runs per image; a block has one run of one strip group.
-    int64_t cur, end;
-    {
-        const int q = blockIdx.x / sgroups, grp = blockIdx.x - q * sgroups;
-        const int n_ = q / rpi, r_ = (q - n_ * rpi) * run;
-        cur = ((int64_t)n_ * sgroups + grp) * H + r_;
-        end = cur + (H - r_ < run ? H - r_ : run);
-    }
-    const uint32_t img_bytes = (uint32_t)H * (uint32_t)W * 64u;
-    const uint32_t rowb = (uint32_t)W * 64u;
-    const int pq = lane >> 2, cs = (lane & 3) ^ ((lane >> 4) & 3);          // LDS position lane & 3 of ring pixel 16 piece + pq holds chunk cs
-    const int p16 = lane >> 2, cch = lane & 3;
-    while (cur < end) {
-        const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * ns + ws_;
-        const int left = (int)(end - cur);
-        const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // output rows r0 .. r0 + L - 1; halo rows r0 - 1 .. r0 + L
-        if (s >= strips) {
-#if FS_SYNC
-            for (int g = 0; g < (L + 2 + FS_R - 1) / FS_R; ++g) __builtin_amdgcn_s_barrier();
-#endif
-            cur += L; continue;
-        }
+    // the waves of a block walk ADJACENT strips over the same rows (nw x 2 KB of every image row between them, at about the same time); the row-major block
+    // order of rs_block_segment: 0.1838 ms at level 0 against 0.1893 for runs cut from the strip-major sequence of rows
+    const RsBlockSeg seg = rs_block_segment(blockIdx.x, (strips + ns - 1) / ns, rpi, run, H);
+    const int n = seg.n, r0 = seg.r0, L = seg.L;                // output rows r0 .. r0 + L - 1; halo rows r0 - 1 .. r0 + L
+    const int s = seg.grp * ns + ws_;
+    const int groups = (L + 2 + FS_R - 1) / FS_R;
+    if (s >= strips) {              // idle wave of the last strip group: only the pacing barriers
+        for (int g = 0; g < groups; ++g) __builtin_amdgcn_s_barrier();
+    } else {
+        const uint32_t img_bytes = (uint32_t)H * (uint32_t)W * 64u;
+        const uint32_t rowb = (uint32_t)W * 64u;
         const int w0 = s * 32;
         const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
         const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * NB), 0, img_bytes * SL, 0x00020000);
-        const int c0 = w0 - 1 + pq, c1 = w0 + 15 + pq, c2 = w0 + 31 + pq;
-        const uint32_t o0 = (c0 >= 0 && c0 < W) ? (uint32_t)(c0 * 64 + cs * 16) : OOB_OFF;
-        const uint32_t o1 = (c1 < W) ? (uint32_t)(c1 * 64 + cs * 16) : OOB_OFF;
-        const uint32_t o2 = (c2 < W) ? (uint32_t)(c2 * 64 + cs * 16) : OOB_OFF;
+        const int c0 = w0 - 1 + (lane >> 2), cs16 = rs_dma_chunk(lane) * 16;
+        const uint32_t o0 = rs_col_off(c0, W, 64, cs16), o1 = rs_col_off(c0 + 16, W, 64, cs16), o2 = rs_col_off(c0 + 32, W, 64, cs16);
         uint32_t so[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) { const int wo = w0 + 16 * u + p16; so[u] = wo < W ? (uint32_t)(wo * (64 * SL) + slab * 64 + cch * 16) : OOB_OFF; }
-        const uint32_t row0 = (uint32_t)(r0 - 1) * rowb;
+        rs_store_offs(so, w0, W, 64 * SL, slab * 64 + (lane & 3) * 16, lane);
+        const uint32_t row0 = (uint32_t)(r0 - 1) * rowb;            // r0 = 0: wraps far beyond the descriptor range -> zeros (the padding row)
         auto issue = [&](int a, int slot) {
             const uint32_t ro = row0 + (uint32_t)a * rowb;
             const bool xin = a <= L + 1;
@@ -1186,37 +1126,25 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
         };
 #pragma unroll
         for (int a = 0; a < FS_P; ++a) issue(a, a);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (FS_P - 1)) : "memory");
+        rs_wait_row<3, FS_P>();
         bf16x8 X[3][2], Xn[3][2];
 #pragma unroll
         for (int d = 0; d < 3; ++d)
 #pragma unroll
             for (int kc = 0; kc < 2; ++kc) X[d][kc] = *reinterpret_cast<const bf16x8*>(xB[d][kc]);
         f32x16 acc[3];
-        const int groups = (L + 2 + FS_R - 1) / FS_R;
         for (int g = 0; g < groups; ++g) {
-#if FS_SYNC
             __builtin_amdgcn_s_barrier();           // keeps the four strips of a block on the same rows (no data is shared)
-#endif
 #pragma unroll
             for (int j = 0; j < FS_R; ++j) {
                 const int a = g * FS_R + j;
                 issue(a + FS_P, (j + FS_P) % FS_R);
-                // Halo row a + 1 has landed once at most the 3 (FS_P - 1) younger DMA pieces are outstanding.  The 2 (FS_P - 1) younger stores are NOT added to the
-                // count: loads retire in order among loads, but a store whose lanes are all out of range (rows behind the segment, the upper half of a narrow last
-                // strip) is dropped and acknowledged at once -- counting it let the fragment reads of the first rows of a segment overtake their DMA (full-size test).
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (FS_P - 1)) : "memory");
+                rs_wait_row<3, FS_P>();             // halo row a + 1 has landed
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
 #pragma unroll
                     for (int kc = 0; kc < 2; ++kc) Xn[d][kc] = *reinterpret_cast<const bf16x8*>(xB[d][kc] + ((j + 1) % FS_R) * FS_ROWB);
-                {           // output row a starts at the bias of this lane's 16 channels
-                    float4 bq[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const float4*>(sBl + 8 * q + 4 * hh);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { acc[j % 3][4 * q] = bq[q].x; acc[j % 3][4 * q + 1] = bq[q].y; acc[j % 3][4 * q + 2] = bq[q].z; acc[j % 3][4 * q + 3] = bq[q].w; }
-                }
+                rs_acc_bias(acc[j % 3], sBl, hh);   // output row a starts
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy)          // halo row a is tap row dy of output row a - dy
@@ -1226,11 +1154,11 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
                         for (int kc = 0; kc < 2; ++kc)
                             acc[(j + 3 - dy) % 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[dy * 3 + d][kc], X[d][kc], acc[(j + 3 - dy) % 3], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                // output row a - 2 is complete: pack, transpose through the free ring slot (the one halo row a + 8 will land in), two 1 KB stores
+                // output row a - 2 is complete: pack, transpose through the free ring slot (that of halo row a - 1: rs_ring_ok), two 1 KB stores
                 const int orow = a - 2;
                 const bool ovalid = orow >= 0 && orow < L;
                 const f32x16& A = acc[(j + 1) % 3];
-                unsigned char* sc = ring + ((j + 8) % FS_R) * FS_ROWB;
+                unsigned char* sc = ring + ((j + FS_R - 1) % FS_R) * FS_ROWB;
                 uint2 o[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -1243,29 +1171,15 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
                     }
                     o[q].x = pack_bf16x2(v4[0], v4[1]); o[q].y = pack_bf16x2(v4[2], v4[3]);
                 }
-                const int f = (r >> 1) & 3;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(sc + r * 64 + ((q ^ f) << 4) + hh * 8) = o[q];
-                wave_lds_fence();
                 u32x4 pend[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(sc + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
-                wave_lds_fence();
+                rs_transpose_row(sc, o, pend, lane);
                 const uint32_t oro = (uint32_t)(r0 + orow) * (rowb * SL);
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const bool inb = ovalid && so[u] != OOB_OFF;
                     __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, inb ? so[u] + oro : OOB_OFF, 0, 0);
-                    if (ST) {
-                        if (inb) {
-                            const uint32_t wv[4] = {pend[u][0], pend[u][1], pend[u][2], pend[u][3]};
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                float u0 = __uint_as_float(wv[k] << 16), u1 = __uint_as_float(wv[k] & 0xffff0000u);
-                                if (STATS == 2) { u0 = fmaxf(u0, 0.01f * u0); u1 = fmaxf(u1, 0.01f * u1); }
-                                ss[2 * k] += u0; sq[2 * k] += u0 * u0; ss[2 * k + 1] += u1; sq[2 * k + 1] += u1 * u1;
-                            }
-                        }
+                    if constexpr (ST) {
+                        if (inb) rs_stats_add<STATS == 2>(ss, sq, pend[u]);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1275,24 +1189,13 @@ k_conv32_fwd33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
                     for (int kc = 0; kc < 2; ++kc) X[d][kc] = Xn[d][kc];
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cur += L;
+        rs_wait_all();
     }
-    if (ST) {
-        // a lane owns channels 8 (lane & 3) ..+7 of the pixels it stored: butterfly over lane bits 2..5, per-wave LDS slots, fp64 atomics (as k_conv32_mfma)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (ST) {         // per-wave slots (rs_stats_fold), then fp64 atomics
+        rs_wait_all();
         __syncthreads();
-        float* red = sB + NB;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float a = ss[k], b = sq[k];
-#pragma unroll
-            for (int o = 32; o > 2; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-            if (lane < 4) {
-                red[wave * 64 + 8 * lane + k] = a;
-                red[wave * 64 + 32 + 8 * lane + k] = b;
-            }
-        }
+        float* red = reinterpret_cast<float*>(smem + LD.part);
+        rs_stats_fold(ss, sq, red + wave * 64, lane);
         __syncthreads();
         if (tid < 64 * SL) {
             const int o = tid >> 6, c = tid & 63;           // output slab o: the waves o, o + SL, ...
@@ -1307,41 +1210,24 @@ static bool conv32_fwd33_stream_launch(const void* x, const void* wp, const floa
                                        bool force, hipStream_t st, const float* aff, int wps) {
     const bool wide = wps > 0;          // 32 -> 64: wave pairs, two strips per block (stat_code 0-2 only)
     const int strips = (W + 31) / 32;
-    const int nw = 4;           // 4 waves x 2 blocks per CU (7 or 8 waves in one block per CU: 0.197 ms against 0.190 at level 0)
-    const int sg = (strips + (wide ? 2 : nw) - 1) / (wide ? 2 : nw);
-    // runs per image: as many as fill the 512 block slots, each at least FS_MIN_RUN rows long (the pipeline fill is FS_P rows per run)
-    int rpi = 512 / (N * sg);
-    if (rpi > H / FS_MIN_RUN) rpi = H / FS_MIN_RUN;
-    if (rpi < 1) rpi = 1;
-    const int run = (H + rpi - 1) / rpi;
-    rpi = (H + run - 1) / run;
-    const int blocks = N * rpi * sg;
-    if (!force && (H < FS_MIN_RUN || blocks < 384)) return false;       // small maps: the tiled kernel
-    const size_t lds = (size_t)nw * FS_R * FS_ROWB + (wide ? 256 : 128) + (size_t)nw * 256;
+    // 4 waves x 2 blocks per CU (7 or 8 waves in one block per CU: 0.197 ms against 0.190 at level 0); runs of at least FS_MIN_RUN rows (the pipeline fill is
+    // FS_P rows per run); small maps: the tiled kernel
+    const RsGridPlan pl = rs_grid_plan(N, H, strips, wide ? 2 : RS_WAVES, 512, FS_MIN_RUN, 384);
+    if (!force && !pl.taken) return false;
 #define FS_LAUNCH(S, WD)                                                                                                                                      \
-    do {                                                                                                                                                      \
-        tcct_launch<k_conv32_fwd33_stream<S, WD>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, \
-                           run, rpi, stats, stats_sq_off, aff, wps);                                                                                             \
-    } while (0)
+    tcct_launch<k_conv32_fwd33_stream<S, WD>, RS_LDS_2PER_CU>(dim3((unsigned)pl.blocks), dim3(FS_T), fs_lds(WD).bytes, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, \
+                                                              W, strips, pl.run, pl.rpi, stats, stats_sq_off, aff, wps)
     if (wide) {
         if (stat_code == 0) FS_LAUNCH(0, true);
         else if (stat_code == 1) FS_LAUNCH(1, true);
         else FS_LAUNCH(2, true);
-        tcct_census_hit(TCCT_CENSUS_FWD33_STREAM);
-        return true;
     }
-#undef FS_LAUNCH
-#define FS_LAUNCH(S)                                                                                                                                          \
-    do {                                                                                                                                                      \
-        tcct_launch<k_conv32_fwd33_stream<S>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, \
-                           run, rpi, stats, stats_sq_off, aff, 0);                                                                                               \
-    } while (0)
-    if (stat_code == 0) FS_LAUNCH(0);
-    else if (stat_code == 1) FS_LAUNCH(1);
-    else if (stat_code == 2) FS_LAUNCH(2);
-    else if (stat_code == 4) FS_LAUNCH(4);
-    else if (stat_code == 5) FS_LAUNCH(5);
-    else FS_LAUNCH(6);
+    else if (stat_code == 0) FS_LAUNCH(0, false);
+    else if (stat_code == 1) FS_LAUNCH(1, false);
+    else if (stat_code == 2) FS_LAUNCH(2, false);
+    else if (stat_code == 4) FS_LAUNCH(4, false);
+    else if (stat_code == 5) FS_LAUNCH(5, false);
+    else FS_LAUNCH(6, false);
 #undef FS_LAUNCH
     tcct_census_hit(TCCT_CENSUS_FWD33_STREAM);
     return true;
@@ -1354,156 +1240,107 @@ static bool conv32_fwd33_stream_launch(const void* x, const void* wp, const floa
 // 153 KB: ONE block of four waves per CU, one wave per SIMD with the 512-register budget, everything in registers as in the 32 -> 32 kernel (no weight image in LDS, no
 // block barrier beyond the pacing one).  Seven rows x 4352 B x 4 waves = 119 KB are in flight per CU -- more than the 2 x 4 x 7 x 2176 B of the 32 -> 32 kernel.
 // Ring image: chunk c (16 B = 8 channels, 0-7) of ring pixel P sits at position c ^ ((P >> 1) & 7) of its 128-byte row: the sixteen pixels of a ds_read_b128 lane group
-// hit sixteen distinct 16-byte bank slots at dx = 0, 1, 2.  A halo row is five DMA pieces of 8 pixels (the last one 2 pixels): `s_waitcnt vmcnt(5 (DG_P - 1))`, stores not
-// counted (see k_conv32_fwd33_stream).
-#define DG_R 9
-#define DG_P 7
-#define DG_ROWB 4352            // 34 halo pixels x 128 B
+// hit sixteen distinct 16-byte bank slots at dx = 0, 1, 2.  A halo row is five DMA pieces of 8 pixels (the last one 2 pixels).
 __global__ void __launch_bounds__(FS_T, 1)      // one wave per SIMD: <= 512 VGPRs
 k_conv64x32_dgrad33_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, int wps, bf16* __restrict__ y, int N, int H, int W, int strips, int run, int rpi) {
+    static_assert(rs_ring_ok(DG_R, DG_P, 3) && dg_lds_bytes() <= RS_LDS_1PER_CU, "k_conv64x32_dgrad33_stream: ring invariant / LDS cap");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int nw = blockDim.x >> 6;             // waves = adjacent strips per block (4)
     unsigned char* ring = smem + wave * (DG_R * DG_ROWB);
-    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
-    bf16x8 Wf[2][9][2];         // A operands: input slab sl, row co = r, input channels 32 sl + 8 hh + 16 half ..+7 of tap t
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl)
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int kc = 0; kc < 2; ++kc) Wf[sl][t][kc] = *reinterpret_cast<const bf16x8*>(wp + (size_t)sl * wps + (t * 32 + r) * 32 + (hh + 2 * kc) * 8);
+    const uint32_t ring_lds = rs_ring_lds(ring);
+    bf16x8 Wf[2][9][2];         // [input slab sl]: input channels 32 sl + 8 hh + 16 half ..+7
+    rs_load_wfrag<9>(Wf[0], wp, r, hh);
+    rs_load_wfrag<9>(Wf[1], wp + wps, r, hh);
     const unsigned char* xB[3][4];          // [dx][2 sl + half]
 #pragma unroll
     for (int d = 0; d < 3; ++d)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { const int P = r + d; xB[d][c] = ring + P * 128 + (((hh + 2 * c) ^ ((P >> 1) & 7)) << 4); }
-    const int sgroups = (strips + nw - 1) / nw;
-    int64_t cur, end;
-    {
-        const int q = blockIdx.x / sgroups, grp = blockIdx.x - q * sgroups;
-        const int n_ = q / rpi, r_ = (q - n_ * rpi) * run;
-        cur = ((int64_t)n_ * sgroups + grp) * H + r_;
-        end = cur + (H - r_ < run ? H - r_ : run);
+        for (int c = 0; c < 4; ++c) xB[d][c] = ring + rs_frag_off128(r + d, hh + 2 * c);
+    const RsBlockSeg seg = rs_block_segment(blockIdx.x, (strips + RS_WAVES - 1) / RS_WAVES, rpi, run, H);
+    const int n = seg.n, r0 = seg.r0, L = seg.L;                // output rows r0 .. r0 + L - 1; halo rows r0 - 1 .. r0 + L
+    const int s = seg.grp * RS_WAVES + wave;
+    const int groups = (L + 2 + DG_R - 1) / DG_R;
+    if (s >= strips) {              // idle wave of the last strip group: only the pacing barriers
+        for (int g = 0; g < groups; ++g) __builtin_amdgcn_s_barrier();
+        return;
     }
     const uint32_t ximg = (uint32_t)H * (uint32_t)W * 128u, yimg = (uint32_t)H * (uint32_t)W * 64u;
     const uint32_t xrowb = (uint32_t)W * 128u, yrowb = (uint32_t)W * 64u;
-    const int p8 = lane >> 3;               // DMA piece k: ring pixel 8 k + p8, LDS position lane & 7 holds chunk (lane & 7) ^ ((4 k + (lane >> 4)) & 7)
-    const int p16 = lane >> 2, cch = lane & 3;
-    while (cur < end) {
-        const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * nw + wave;
-        const int left = (int)(end - cur);
-        const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // output rows r0 .. r0 + L - 1; halo rows r0 - 1 .. r0 + L
-        if (s >= strips) {
-#if FS_SYNC
-            for (int g = 0; g < (L + 2 + DG_R - 1) / DG_R; ++g) __builtin_amdgcn_s_barrier();
-#endif
-            cur += L; continue;
-        }
-        const int w0 = s * 32;
-        const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 64, ximg);
-        const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, yimg, 0x00020000);
-        uint32_t po[5];
+    const int w0 = s * 32;
+    const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 64, ximg);
+    const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, yimg, 0x00020000);
+    uint32_t po[5];             // DMA piece k: ring pixel 8 k + (lane >> 3), LDS position lane & 7 holds chunk (lane & 7) ^ ((4 k + (lane >> 4)) & 7)
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int col = w0 - 1 + 8 * k + p8, cs = (lane & 7) ^ ((4 * k + (lane >> 4)) & 7);
-            po[k] = (col >= 0 && col < W) ? (uint32_t)(col * 128 + cs * 16) : OOB_OFF;
-        }
-        uint32_t so[2];
+    for (int k = 0; k < 5; ++k) po[k] = rs_col_off(w0 - 1 + 8 * k + (lane >> 3), W, 128, ((lane & 7) ^ ((4 * k + (lane >> 4)) & 7)) * 16);
+    uint32_t so[2];
+    rs_store_offs(so, w0, W, 64, (lane & 3) * 16, lane);
+    const uint32_t row0 = (uint32_t)(r0 - 1) * xrowb;
+    auto issue = [&](int a, int slot) {
+        const uint32_t ro = row0 + (uint32_t)a * xrowb;
+        const bool xin = a <= L + 1;
+        const uint32_t base = ring_lds + (uint32_t)(slot * DG_ROWB);
 #pragma unroll
-        for (int u = 0; u < 2; ++u) { const int wo = w0 + 16 * u + p16; so[u] = wo < W ? (uint32_t)(wo * 64 + cch * 16) : OOB_OFF; }
-        const uint32_t row0 = (uint32_t)(r0 - 1) * xrowb;
-        auto issue = [&](int a, int slot) {
-            const uint32_t ro = row0 + (uint32_t)a * xrowb;
-            const bool xin = a <= L + 1;
-            const uint32_t base = ring_lds + (uint32_t)(slot * DG_ROWB);
+        for (int k = 0; k < 4; ++k) lds_dma16(rx, xin ? po[k] + ro : OOB_OFF, base + 1024u * k);
+        if (lane < 16) lds_dma16(rx, xin ? po[4] + ro : OOB_OFF, base + 4096u);
+    };
 #pragma unroll
-            for (int k = 0; k < 4; ++k) lds_dma16(rx, xin ? po[k] + ro : OOB_OFF, base + 1024u * k);
-            if (lane < 16) lds_dma16(rx, xin ? po[4] + ro : OOB_OFF, base + 4096u);
-        };
+    for (int a = 0; a < DG_P; ++a) issue(a, a);
+    rs_wait_row<5, DG_P>();
+    bf16x8 X[3][4], Xn[3][4];
 #pragma unroll
-        for (int a = 0; a < DG_P; ++a) issue(a, a);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(5 * (DG_P - 1)) : "memory");
-        bf16x8 X[3][4], Xn[3][4];
+    for (int d = 0; d < 3; ++d)
 #pragma unroll
-        for (int d = 0; d < 3; ++d)
+        for (int c = 0; c < 4; ++c) X[d][c] = *reinterpret_cast<const bf16x8*>(xB[d][c]);
+    f32x16 acc[3];
+    for (int g = 0; g < groups; ++g) {
+        __builtin_amdgcn_s_barrier();           // keeps the four strips of a block on the same rows (no data is shared)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) X[d][c] = *reinterpret_cast<const bf16x8*>(xB[d][c]);
-        f32x16 acc[3];
-        const int groups = (L + 2 + DG_R - 1) / DG_R;
-        for (int g = 0; g < groups; ++g) {
-#if FS_SYNC
-            __builtin_amdgcn_s_barrier();           // keeps the four strips of a block on the same rows (no data is shared)
-#endif
+        for (int j = 0; j < DG_R; ++j) {
+            const int a = g * DG_R + j;
+            issue(a + DG_P, (j + DG_P) % DG_R);
+            rs_wait_row<5, DG_P>();             // halo row a + 1 has landed
 #pragma unroll
-            for (int j = 0; j < DG_R; ++j) {
-                const int a = g * DG_R + j;
-                issue(a + DG_P, (j + DG_P) % DG_R);
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(5 * (DG_P - 1)) : "memory");         // halo row a + 1 has landed (stores not counted)
+            for (int d = 0; d < 3; ++d)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) Xn[d][c] = *reinterpret_cast<const bf16x8*>(xB[d][c] + ((j + 1) % DG_R) * DG_ROWB);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc[j % 3][k] = 0.f;          // output row a starts (an input gradient has no bias)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int dy = 0; dy < 3; ++dy)          // halo row a is tap row dy of output row a - dy
 #pragma unroll
                 for (int d = 0; d < 3; ++d)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) Xn[d][c] = *reinterpret_cast<const bf16x8*>(xB[d][c] + ((j + 1) % DG_R) * DG_ROWB);
+                    for (int c = 0; c < 4; ++c)
+                        acc[(j + 3 - dy) % 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[c >> 1][dy * 3 + d][c & 1], X[d][c], acc[(j + 3 - dy) % 3], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            // output row a - 2 is complete: pack, transpose through the free ring slot (that of halo row a - 1: rs_ring_ok), two 1 KB stores
+            const int orow = a - 2;
+            const bool ovalid = orow >= 0 && orow < L;
+            uint2 o[4];
+            rs_pack_row(o, acc[(j + 1) % 3]);
+            u32x4 pend[2];
+            rs_transpose_row(ring + ((j + DG_R - 1) % DG_R) * DG_ROWB, o, pend, lane);
+            const uint32_t oro = (uint32_t)(r0 + orow) * yrowb;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) acc[j % 3][k] = 0.f;          // output row a starts (an input gradient has no bias)
-                __builtin_amdgcn_sched_barrier(0);
+            for (int u = 0; u < 2; ++u) __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, (ovalid && so[u] != OOB_OFF) ? so[u] + oro : OOB_OFF, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int dy = 0; dy < 3; ++dy)          // halo row a is tap row dy of output row a - dy
+            for (int d = 0; d < 3; ++d)
 #pragma unroll
-                    for (int d = 0; d < 3; ++d)
-#pragma unroll
-                        for (int c = 0; c < 4; ++c)
-                            acc[(j + 3 - dy) % 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[c >> 1][dy * 3 + d][c & 1], X[d][c], acc[(j + 3 - dy) % 3], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                // output row a - 2 is complete: pack, transpose through the free ring slot (the one halo row a + 8 will land in), two 1 KB stores
-                const int orow = a - 2;
-                const bool ovalid = orow >= 0 && orow < L;
-                const f32x16& A = acc[(j + 1) % 3];
-                unsigned char* sc = ring + ((j + 8) % DG_R) * DG_ROWB;
-                uint2 o[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { o[q].x = pack_bf16x2(A[4 * q], A[4 * q + 1]); o[q].y = pack_bf16x2(A[4 * q + 2], A[4 * q + 3]); }
-                const int f = (r >> 1) & 3;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(sc + r * 64 + ((q ^ f) << 4) + hh * 8) = o[q];
-                wave_lds_fence();
-                u32x4 pend[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(sc + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
-                wave_lds_fence();
-                const uint32_t oro = (uint32_t)(r0 + orow) * yrowb;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const bool inb = ovalid && so[u] != OOB_OFF;
-                    __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, inb ? so[u] + oro : OOB_OFF, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int d = 0; d < 3; ++d)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) X[d][c] = Xn[d][c];
-            }
+                for (int c = 0; c < 4; ++c) X[d][c] = Xn[d][c];
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cur += L;
     }
+    rs_wait_all();
 }
 /* true when the row-stream kernel was launched (maps whose waves get >= FS_MIN_RUN rows and that fill most CUs, or force) */
 static bool conv64x32_dgrad33_stream_launch(const void* dy, const void* wp, int wps, void* dx, int N, int H, int W, bool force, hipStream_t st) {
     const int strips = (W + 31) / 32;
-    const int nw = 4;
-    const int sg = (strips + nw - 1) / nw;
-    int rpi = 256 / (N * sg);           // one block per CU
-    if (rpi > H / FS_MIN_RUN) rpi = H / FS_MIN_RUN;
-    if (rpi < 1) rpi = 1;
-    const int run = (H + rpi - 1) / rpi;
-    rpi = (H + run - 1) / run;
-    const int blocks = N * rpi * sg;
-    if (!force && (H < FS_MIN_RUN || blocks < 192)) return false;
-    const size_t lds = (size_t)nw * DG_R * DG_ROWB;
-    tcct_launch<k_conv64x32_dgrad33_stream, 160 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), lds, st, (const bf16*)dy, (const bf16*)wp, wps, (bf16*)dx, N, H, W, strips, run, rpi);
+    const RsGridPlan pl = rs_grid_plan(N, H, strips, RS_WAVES, 256, FS_MIN_RUN, 192);           // 256 slots: one block per CU
+    if (!force && !pl.taken) return false;
+    tcct_launch<k_conv64x32_dgrad33_stream, RS_LDS_1PER_CU>(dim3((unsigned)pl.blocks), dim3(FS_T), dg_lds_bytes(), st, (const bf16*)dy, (const bf16*)wp, wps, (bf16*)dx, N, H, W, strips,
+                                                            pl.run, pl.rpi);
     tcct_census_hit(TCCT_CENSUS_FWD33_STREAM);
     return true;
 }
@@ -1512,145 +1349,99 @@ static bool conv64x32_dgrad33_stream_launch(const void* dy, const void* wp, int 
 // The horizontal cross convolutions (reference nets/tcct.py:814-818; K = 13, 11, 9 at levels 0, 1, 2) in the row-stream structure of k_conv32_fwd33_stream.  A row is
 // self-contained here (no rolling window): halo row = 32 + K - 1 pixels, one accumulator, 2 K MFMAs per row in the tiled kernel's (dx, half) order on the same
 // MFMA => BIT-IDENTICAL to k_conv32_mfma<false, 0, 1, K>.  The 2 K weight fragments and the 2 K per-lane fragment addresses live in registers; ring of 7 rows, 5 in flight.
-#define F1_R 7
-#define F1_P 5
 template <int K>
 __global__ void __launch_bounds__(FS_T, 2)
 k_conv32_fwd1k_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, const float* __restrict__ bias, bf16* __restrict__ y,
                       int N, int H, int W, int strips, int run, int rpi) {
-    constexpr int LWP = 32 + K - 1, ROWB = LWP * 64, TAIL = LWP - 32;         // halo pixels per row, ring bytes per row, pixels of the third DMA piece
+    constexpr int LWP = 32 + K - 1, ROWB = f1_rowb(K), TAIL = LWP - 32;         // halo pixels per row, ring bytes per row, pixels of the third DMA piece
     static_assert(TAIL >= 1 && TAIL <= 16 && ROWB >= 2048, "1 x K row streams: 3 <= K <= 17");
+    static_assert(rs_ring_ok(F1_R, F1_P) && f1_lds(K).bytes <= RS_LDS_2PER_CU, "k_conv32_fwd1k_stream: ring invariant / LDS cap");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int nw = blockDim.x >> 6;
     unsigned char* ring = smem + wave * (F1_R * ROWB);
-    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
-    float* sB = reinterpret_cast<float*>(smem + nw * F1_R * ROWB);
+    const uint32_t ring_lds = rs_ring_lds(ring);
+    float* sB = reinterpret_cast<float*>(smem + f1_lds(K).bias);
     bf16x8 Wf[K][2];
-#pragma unroll
-    for (int t = 0; t < K; ++t)
-#pragma unroll
-        for (int kc = 0; kc < 2; ++kc) Wf[t][kc] = *reinterpret_cast<const bf16x8*>(wp + (t * 32 + r) * 32 + (hh + 2 * kc) * 8);
+    rs_load_wfrag<K>(Wf, wp, r, hh);
     if (tid < 32) sB[tid] = bias ? bias[tid] : 0.f;
     __syncthreads();
-    uint32_t xo_[K][2];          // byte offset in a ring row of this lane's fragment of tap dx, half kc (chunk c of ring pixel P sits at position c ^ ((P >> 2) & 3))
+    uint32_t xo_[K][2];          // byte offset in a ring row of this lane's fragment of tap dx, half kc
 #pragma unroll
     for (int d = 0; d < K; ++d)
 #pragma unroll
-        for (int kc = 0; kc < 2; ++kc) { const int P = r + d; xo_[d][kc] = (uint32_t)(P * 64 + (((hh + 2 * kc) ^ ((P >> 2) & 3)) << 4)); }
-    const int sgroups = (strips + nw - 1) / nw;
-    int64_t cur, end;
-    {
-        const int q = blockIdx.x / sgroups, grp = blockIdx.x - q * sgroups;
-        const int n_ = q / rpi, r_ = (q - n_ * rpi) * run;
-        cur = ((int64_t)n_ * sgroups + grp) * H + r_;
-        end = cur + (H - r_ < run ? H - r_ : run);
-    }
+        for (int kc = 0; kc < 2; ++kc) xo_[d][kc] = rs_frag_off64(r + d, hh + 2 * kc);
+    const RsBlockSeg seg = rs_block_segment(blockIdx.x, (strips + RS_WAVES - 1) / RS_WAVES, rpi, run, H);
+    const int n = seg.n, r0 = seg.r0, L = seg.L;                // rows r0 .. r0 + L - 1
+    const int s = seg.grp * RS_WAVES + wave;
+    if (s >= strips) return;        // idle wave of the last strip group (no barrier follows)
     const uint32_t img_bytes = (uint32_t)H * (uint32_t)W * 64u;
     const uint32_t rowb = (uint32_t)W * 64u;
-    const int pq = lane >> 2, cs = (lane & 3) ^ ((lane >> 4) & 3);
-    const int p16 = lane >> 2, cch = lane & 3;
     constexpr int PADL = (K - 1) / 2;
-    while (cur < end) {
-        const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * nw + wave;
-        const int left = (int)(end - cur);
-        const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // rows r0 .. r0 + L - 1
-        if (s >= strips) { cur += L; continue; }
-        const int w0 = s * 32;
-        const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
-        const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
-        const int c0 = w0 - PADL + pq, c1 = c0 + 16, c2 = c0 + 32;
-        const uint32_t o0 = (c0 >= 0 && c0 < W) ? (uint32_t)(c0 * 64 + cs * 16) : OOB_OFF;
-        const uint32_t o1 = (c1 >= 0 && c1 < W) ? (uint32_t)(c1 * 64 + cs * 16) : OOB_OFF;
-        const uint32_t o2 = (c2 < W) ? (uint32_t)(c2 * 64 + cs * 16) : OOB_OFF;
-        uint32_t so[2];
+    const int w0 = s * 32;
+    const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
+    const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
+    const int c0 = w0 - PADL + (lane >> 2), cs16 = rs_dma_chunk(lane) * 16;
+    const uint32_t o0 = rs_col_off(c0, W, 64, cs16), o1 = rs_col_off(c0 + 16, W, 64, cs16), o2 = rs_col_off(c0 + 32, W, 64, cs16);
+    uint32_t so[2];
+    rs_store_offs(so, w0, W, 64, (lane & 3) * 16, lane);
+    const uint32_t row0 = (uint32_t)r0 * rowb;
+    auto issue = [&](int a, int slot) {
+        const uint32_t ro = row0 + (uint32_t)a * rowb;
+        const bool xin = a < L;
+        const uint32_t base = ring_lds + (uint32_t)(slot * ROWB);
+        lds_dma16(rx, xin ? o0 + ro : OOB_OFF, base);
+        lds_dma16(rx, xin ? o1 + ro : OOB_OFF, base + 1024u);
+        if (lane < 4 * TAIL) lds_dma16(rx, xin ? o2 + ro : OOB_OFF, base + 2048u);
+    };
 #pragma unroll
-        for (int u = 0; u < 2; ++u) { const int wo = w0 + 16 * u + p16; so[u] = wo < W ? (uint32_t)(wo * 64 + cch * 16) : OOB_OFF; }
-        const uint32_t row0 = (uint32_t)r0 * rowb;
-        auto issue = [&](int a, int slot) {
-            const uint32_t ro = row0 + (uint32_t)a * rowb;
-            const bool xin = a < L;
-            const uint32_t base = ring_lds + (uint32_t)(slot * ROWB);
-            lds_dma16(rx, xin ? o0 + ro : OOB_OFF, base);
-            lds_dma16(rx, xin ? o1 + ro : OOB_OFF, base + 1024u);
-            if (lane < 4 * TAIL) lds_dma16(rx, xin ? o2 + ro : OOB_OFF, base + 2048u);
-        };
+    for (int a = 0; a < F1_P; ++a) issue(a, a);
+    const int groups = (L + F1_R - 1) / F1_R;
+    for (int g = 0; g < groups; ++g) {
 #pragma unroll
-        for (int a = 0; a < F1_P; ++a) issue(a, a);
-        const int groups = (L + F1_R - 1) / F1_R;
-        for (int g = 0; g < groups; ++g) {
+        for (int j = 0; j < F1_R; ++j) {
+            const int a = g * F1_R + j;
+            rs_wait_row<3, F1_P>();             // row a has landed: only rows a + 1 .. a + F1_P - 1 are outstanding
+            const unsigned char* rowp = ring + j * ROWB;
+            f32x16 acc;
+            rs_acc_bias(acc, sB, hh);
+            bf16x8 F[2][2];
+            F[0][0] = *reinterpret_cast<const bf16x8*>(rowp + xo_[0][0]);
+            F[0][1] = *reinterpret_cast<const bf16x8*>(rowp + xo_[0][1]);
 #pragma unroll
-            for (int j = 0; j < F1_R; ++j) {
-                const int a = g * F1_R + j;
-                // row a has landed once only the 3 (F1_P - 1) pieces of rows a + 1 .. a + F1_P - 1 are outstanding (stores are not counted: k_conv32_fwd33_stream)
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (F1_P - 1)) : "memory");
-                const unsigned char* rowp = ring + j * ROWB;
-                f32x16 acc;
-                {
-                    float4 bq[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const float4*>(sB + 8 * q + 4 * hh);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { acc[4 * q] = bq[q].x; acc[4 * q + 1] = bq[q].y; acc[4 * q + 2] = bq[q].z; acc[4 * q + 3] = bq[q].w; }
+            for (int d = 0; d < K; ++d) {
+                if (d + 1 < K) {
+                    F[(d + 1) & 1][0] = *reinterpret_cast<const bf16x8*>(rowp + xo_[d + 1][0]);
+                    F[(d + 1) & 1][1] = *reinterpret_cast<const bf16x8*>(rowp + xo_[d + 1][1]);
                 }
-                bf16x8 F[2][2];
-                F[0][0] = *reinterpret_cast<const bf16x8*>(rowp + xo_[0][0]);
-                F[0][1] = *reinterpret_cast<const bf16x8*>(rowp + xo_[0][1]);
-#pragma unroll
-                for (int d = 0; d < K; ++d) {
-                    if (d + 1 < K) {
-                        F[(d + 1) & 1][0] = *reinterpret_cast<const bf16x8*>(rowp + xo_[d + 1][0]);
-                        F[(d + 1) & 1][1] = *reinterpret_cast<const bf16x8*>(rowp + xo_[d + 1][1]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[d][0], F[d & 1][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[d][1], F[d & 1][1], acc, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                // the DMA of row a + F1_P goes to slot (j + F1_P) % F1_R; slot (j + F1_R - 1) % F1_R (row a - 1, consumed) is the transpose scratch of this row
-                issue(a + F1_P, (j + F1_P) % F1_R);
-                const bool ovalid = a < L;
-                unsigned char* sc = ring + ((j + F1_R - 1) % F1_R) * ROWB;
-                uint2 o[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { o[q].x = pack_bf16x2(acc[4 * q], acc[4 * q + 1]); o[q].y = pack_bf16x2(acc[4 * q + 2], acc[4 * q + 3]); }
-                const int f = (r >> 1) & 3;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(sc + r * 64 + ((q ^ f) << 4) + hh * 8) = o[q];
-                wave_lds_fence();
-                u32x4 pend[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(sc + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
-                wave_lds_fence();
-                const uint32_t oro = (uint32_t)(r0 + a) * rowb;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, (ovalid && so[u] != OOB_OFF) ? so[u] + oro : OOB_OFF, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[d][0], F[d & 1][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Wf[d][1], F[d & 1][1], acc, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
+            // the DMA of row a + F1_P goes to slot (j + F1_P) % F1_R; slot (j + F1_R - 1) % F1_R (row a - 1, consumed) is the transpose scratch of this row
+            issue(a + F1_P, (j + F1_P) % F1_R);
+            const bool ovalid = a < L;
+            uint2 o[4];
+            rs_pack_row(o, acc);
+            u32x4 pend[2];
+            rs_transpose_row(ring + ((j + F1_R - 1) % F1_R) * ROWB, o, pend, lane);
+            const uint32_t oro = (uint32_t)(r0 + a) * rowb;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, (ovalid && so[u] != OOB_OFF) ? so[u] + oro : OOB_OFF, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cur += L;
     }
+    rs_wait_all();
 }
 /* plain 32-channel 1 x K (K = 13, 11, 9; no slabs, no accumulate, no statistics): true when the row-stream kernel was launched */
 static bool conv32_fwd1k_stream_launch(const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int K, bool force, hipStream_t st) {
     const int strips = (W + 31) / 32;
-    const int nw = 4;
-    const int sg = (strips + nw - 1) / nw;
-    int rpi = 512 / (N * sg);
-    if (rpi > H / FS_MIN_RUN) rpi = H / FS_MIN_RUN;
-    if (rpi < 1) rpi = 1;
-    const int run = (H + rpi - 1) / rpi;
-    rpi = (H + run - 1) / run;
-    const int blocks = N * rpi * sg;
-    if (!force && (H < FS_MIN_RUN || blocks < 384)) return false;
+    const RsGridPlan pl = rs_grid_plan(N, H, strips, RS_WAVES, 512, FS_MIN_RUN, 384);
+    if (!force && !pl.taken) return false;
 #define F1_LAUNCH(KK)                                                                                                                                          \
-    do {                                                                                                                                                      \
-        tcct_launch<k_conv32_fwd1k_stream<KK>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), (size_t)nw * F1_R * (32 + KK - 1) * 64 + 128, st, (const bf16*)x, (const bf16*)wp, \
-                           bias, (bf16*)y, N, H, W, strips, run, rpi);                                                                                      \
-    } while (0)
+    tcct_launch<k_conv32_fwd1k_stream<KK>, RS_LDS_2PER_CU>(dim3((unsigned)pl.blocks), dim3(FS_T), f1_lds(KK).bytes, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, \
+                                                           strips, pl.run, pl.rpi)
     if (K == 13) F1_LAUNCH(13);
     else if (K == 11) F1_LAUNCH(11);
     else if (K == 9) F1_LAUNCH(9);
@@ -1664,20 +1455,19 @@ static bool conv32_fwd1k_stream_launch(const void* x, const void* wp, const floa
 // fragments of the last K rows stay in a REGISTER window (K x 2 fragments, 104 VGPRs for K = 13; the unrolled body's position j = a mod K names the registers) and
 // each halo row is read from LDS exactly once; the 2 K weight fragments come from a block-shared LDS image (the tiled kernel's swizzled rows) per output row.
 // MFMAs in the tiled kernel's (dy, half) order => BIT-IDENTICAL to k_conv32_mfma<true, 0, K, 1>.  Ring of 6 rows per wave (runtime slot index), 4 in flight.
-#define FV_R 6
-#define FV_P 4
 template <int K>
 __global__ void __launch_bounds__(FS_T, 2)
 k_conv32_fwdk1_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, const float* __restrict__ bias, bf16* __restrict__ y,
                       int N, int H, int W, int strips, int run, int rpi) {
+    static_assert(rs_ring_ok(FV_R, FV_P) && fv_lds(K).bytes <= RS_LDS_2PER_CU, "k_conv32_fwdk1_stream: ring invariant / LDS cap");
+    constexpr FvLds LD = fv_lds(K);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int nw = blockDim.x >> 6;
     unsigned char* sW = smem;                                   // K taps x 32 rows x 64 B, chunks XOR-swizzled by (row >> 2) & 3
-    unsigned char* ring = smem + K * 2048 + wave * (FV_R * 2048);
-    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
-    float* sB = reinterpret_cast<float*>(smem + K * 2048 + nw * FV_R * 2048);
+    unsigned char* ring = smem + LD.ring + wave * (FV_R * FV_ROWB);
+    const uint32_t ring_lds = rs_ring_lds(ring);
+    float* sB = reinterpret_cast<float*>(smem + LD.bias);
     for (int i = tid; i < K * 32 * 4; i += blockDim.x) {
         const int row = i >> 2, c = i & 3;
         *reinterpret_cast<uint4*>(sW + row * 64 + ((c ^ ((row >> 2) & 3)) << 4)) = reinterpret_cast<const uint4*>(wp)[i];
@@ -1686,131 +1476,90 @@ k_conv32_fwdk1_stream(const bf16* __restrict__ x, const bf16* __restrict__ wp, c
     __syncthreads();
     const int wsw = (r >> 2) & 3;
     const unsigned char* wA[2] = {sW + r * 64 + ((hh ^ wsw) << 4), sW + r * 64 + (((2 + hh) ^ wsw) << 4)};
-    uint32_t xo_[2];
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) xo_[kc] = (uint32_t)(r * 64 + (((hh + 2 * kc) ^ ((r >> 2) & 3)) << 4));
-    const int sgroups = (strips + nw - 1) / nw;
-    int64_t cur, end;
-    {
-        const int q = blockIdx.x / sgroups, grp = blockIdx.x - q * sgroups;
-        const int n_ = q / rpi, r_ = (q - n_ * rpi) * run;
-        cur = ((int64_t)n_ * sgroups + grp) * H + r_;
-        end = cur + (H - r_ < run ? H - r_ : run);
-    }
+    const uint32_t xo_[2] = {rs_frag_off64(r, hh), rs_frag_off64(r, hh + 2)};
+    const RsBlockSeg seg = rs_block_segment(blockIdx.x, (strips + RS_WAVES - 1) / RS_WAVES, rpi, run, H);
+    const int n = seg.n, r0 = seg.r0, L = seg.L;                // output rows r0 .. r0 + L - 1; halo rows r0 - PADT .. r0 + L - 1 + PADT
+    const int s = seg.grp * RS_WAVES + wave;
+    if (s >= strips) return;        // idle wave of the last strip group (no barrier follows)
     const uint32_t img_bytes = (uint32_t)H * (uint32_t)W * 64u;
     const uint32_t rowb = (uint32_t)W * 64u;
-    const int pq = lane >> 2, cs = (lane & 3) ^ ((lane >> 4) & 3);
-    const int p16 = lane >> 2, cch = lane & 3;
     constexpr int PADT = (K - 1) / 2;
-    while (cur < end) {
-        const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * nw + wave;
-        const int left = (int)(end - cur);
-        const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // output rows r0 .. r0 + L - 1; halo rows r0 - PADT .. r0 + L - 1 + PADT
-        if (s >= strips) { cur += L; continue; }
-        const int w0 = s * 32;
-        const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
-        const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
-        const int c0 = w0 + pq, c1 = c0 + 16;
-        const uint32_t o0 = c0 < W ? (uint32_t)(c0 * 64 + cs * 16) : OOB_OFF;
-        const uint32_t o1 = c1 < W ? (uint32_t)(c1 * 64 + cs * 16) : OOB_OFF;
-        uint32_t so[2];
+    const int w0 = s * 32;
+    const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
+    const __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (int64_t)n * H * W * 32), 0, img_bytes, 0x00020000);
+    const int c0 = w0 + (lane >> 2), cs16 = rs_dma_chunk(lane) * 16;
+    const uint32_t o0 = rs_col_off(c0, W, 64, cs16), o1 = rs_col_off(c0 + 16, W, 64, cs16);
+    uint32_t so[2];
+    rs_store_offs(so, w0, W, 64, (lane & 3) * 16, lane);
+    const uint32_t row0 = (uint32_t)(r0 - PADT) * rowb;        // rows above the image wrap far beyond the descriptor range: zeros (the padding rows)
+    const int nh = L + K - 1;                                   // halo rows of the run
+    int slot_i = 0, slot_d = FV_P % FV_R;                       // ring slots of the row consumed / issued next (run-time: the body is unrolled K-fold, not FV_R-fold)
+    auto issue = [&](int a, int slot) {
+        const uint32_t ro = row0 + (uint32_t)a * rowb;
+        const bool xin = a < nh;
+        const uint32_t base = ring_lds + (uint32_t)(slot * FV_ROWB);
+        lds_dma16(rx, xin ? o0 + ro : OOB_OFF, base);
+        lds_dma16(rx, xin ? o1 + ro : OOB_OFF, base + 1024u);
+    };
 #pragma unroll
-        for (int u = 0; u < 2; ++u) { const int wo = w0 + 16 * u + p16; so[u] = wo < W ? (uint32_t)(wo * 64 + cch * 16) : OOB_OFF; }
-        const uint32_t row0 = (uint32_t)(r0 - PADT) * rowb;        // rows above the image wrap far beyond the descriptor range: zeros (the padding rows)
-        const int nh = L + K - 1;                                   // halo rows of the run
-        int slot_i = 0, slot_d = FV_P % FV_R;                       // ring slots of the row consumed / issued next (runtime: K and FV_R are coprime)
-        auto issue = [&](int a, int slot) {
-            const uint32_t ro = row0 + (uint32_t)a * rowb;
-            const bool xin = a < nh;
-            const uint32_t base = ring_lds + (uint32_t)(slot * 2048);
-            lds_dma16(rx, xin ? o0 + ro : OOB_OFF, base);
-            lds_dma16(rx, xin ? o1 + ro : OOB_OFF, base + 1024u);
-        };
+    for (int a = 0; a < FV_P; ++a) issue(a, a);
+    bf16x8 Xw[K][2];
 #pragma unroll
-        for (int a = 0; a < FV_P; ++a) issue(a, a);
-        bf16x8 Xw[K][2];
+    for (int t = 0; t < K; ++t)
 #pragma unroll
-        for (int t = 0; t < K; ++t)
+        for (int k = 0; k < 8; ++k) { Xw[t][0][k] = (__bf16)0.f; Xw[t][1][k] = (__bf16)0.f; }
+    const int groups = (nh + K - 1) / K;
+    for (int g = 0; g < groups; ++g) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { Xw[t][0][k] = (__bf16)0.f; Xw[t][1][k] = (__bf16)0.f; }
-        const int groups = (nh + K - 1) / K;
-        for (int g = 0; g < groups; ++g) {
+        for (int j = 0; j < K; ++j) {
+            const int a = g * K + j;
+            rs_wait_row<2, FV_P>();             // halo row a has landed
+            const unsigned char* rowp = ring + slot_i * FV_ROWB;
+            Xw[j][0] = *reinterpret_cast<const bf16x8*>(rowp + xo_[0]);
+            Xw[j][1] = *reinterpret_cast<const bf16x8*>(rowp + xo_[1]);
+            f32x16 acc;
+            rs_acc_bias(acc, sB, hh);
+            // output row o = a - (K - 1): tap dy reads halo row o + dy = window position (j + 1 + dy) mod K
+            bf16x8 Af[2][2];
+            Af[0][0] = *reinterpret_cast<const bf16x8*>(wA[0]);
+            Af[0][1] = *reinterpret_cast<const bf16x8*>(wA[1]);
 #pragma unroll
-            for (int j = 0; j < K; ++j) {
-                const int a = g * K + j;
-                asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (FV_P - 1)) : "memory");         // halo row a has landed (DMA pieces only are counted)
-                const unsigned char* rowp = ring + slot_i * 2048;
-                Xw[j][0] = *reinterpret_cast<const bf16x8*>(rowp + xo_[0]);
-                Xw[j][1] = *reinterpret_cast<const bf16x8*>(rowp + xo_[1]);
-                f32x16 acc;
-                {
-                    float4 bq[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const float4*>(sB + 8 * q + 4 * hh);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { acc[4 * q] = bq[q].x; acc[4 * q + 1] = bq[q].y; acc[4 * q + 2] = bq[q].z; acc[4 * q + 3] = bq[q].w; }
+            for (int dy = 0; dy < K; ++dy) {
+                if (dy + 1 < K) {
+                    Af[(dy + 1) & 1][0] = *reinterpret_cast<const bf16x8*>(wA[0] + (dy + 1) * 2048);
+                    Af[(dy + 1) & 1][1] = *reinterpret_cast<const bf16x8*>(wA[1] + (dy + 1) * 2048);
                 }
-                // output row o = a - (K - 1): tap dy reads halo row o + dy = window position (j + 1 + dy) mod K
-                bf16x8 Af[2][2];
-                Af[0][0] = *reinterpret_cast<const bf16x8*>(wA[0]);
-                Af[0][1] = *reinterpret_cast<const bf16x8*>(wA[1]);
-#pragma unroll
-                for (int dy = 0; dy < K; ++dy) {
-                    if (dy + 1 < K) {
-                        Af[(dy + 1) & 1][0] = *reinterpret_cast<const bf16x8*>(wA[0] + (dy + 1) * 2048);
-                        Af[(dy + 1) & 1][1] = *reinterpret_cast<const bf16x8*>(wA[1] + (dy + 1) * 2048);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[dy & 1][0], Xw[(j + 1 + dy) % K][0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[dy & 1][1], Xw[(j + 1 + dy) % K][1], acc, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                issue(a + FV_P, slot_d);
-                const int orow = a - (K - 1);
-                const bool ovalid = orow >= 0 && orow < L;
-                int sc_i = slot_i - 1; if (sc_i < 0) sc_i += FV_R;                  // the slot of halo row a - 1: free until the DMA of row a + FV_R - 1
-                unsigned char* sc = ring + sc_i * 2048;
-                uint2 o[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { o[q].x = pack_bf16x2(acc[4 * q], acc[4 * q + 1]); o[q].y = pack_bf16x2(acc[4 * q + 2], acc[4 * q + 3]); }
-                const int f = (r >> 1) & 3;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *reinterpret_cast<uint2*>(sc + r * 64 + ((q ^ f) << 4) + hh * 8) = o[q];
-                wave_lds_fence();
-                u32x4 pend[2];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) pend[u] = *reinterpret_cast<const u32x4*>(sc + (16 * u + p16) * 64 + ((cch ^ ((p16 >> 1) & 3)) << 4));
-                wave_lds_fence();
-                const uint32_t oro = (uint32_t)(r0 + orow) * rowb;
-#pragma unroll
-                for (int u = 0; u < 2; ++u) __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, (ovalid && so[u] != OOB_OFF) ? so[u] + oro : OOB_OFF, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                slot_i = slot_i + 1 == FV_R ? 0 : slot_i + 1;
-                slot_d = slot_d + 1 == FV_R ? 0 : slot_d + 1;
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[dy & 1][0], Xw[(j + 1 + dy) % K][0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Af[dy & 1][1], Xw[(j + 1 + dy) % K][1], acc, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
             }
+            issue(a + FV_P, slot_d);
+            const int orow = a - (K - 1);
+            const bool ovalid = orow >= 0 && orow < L;
+            int sc_i = slot_i - 1; if (sc_i < 0) sc_i += FV_R;                  // the slot of halo row a - 1: free until the DMA of row a + FV_R - 1
+            uint2 o[4];
+            rs_pack_row(o, acc);
+            u32x4 pend[2];
+            rs_transpose_row(ring + sc_i * FV_ROWB, o, pend, lane);
+            const uint32_t oro = (uint32_t)(r0 + orow) * rowb;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) __builtin_amdgcn_raw_buffer_store_b128(pend[u], ws, (ovalid && so[u] != OOB_OFF) ? so[u] + oro : OOB_OFF, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            slot_i = slot_i + 1 == FV_R ? 0 : slot_i + 1;
+            slot_d = slot_d + 1 == FV_R ? 0 : slot_d + 1;
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cur += L;
     }
+    rs_wait_all();
 }
 /* plain 32-channel K x 1 (K = 13, 11, 9): true when the row-stream kernel was launched */
 static bool conv32_fwdk1_stream_launch(const void* x, const void* wp, const float* bias, void* y, int N, int H, int W, int K, bool force, hipStream_t st) {
     const int strips = (W + 31) / 32;
-    const int nw = 4;
-    const int sg = (strips + nw - 1) / nw;
-    int rpi = 512 / (N * sg);
-    if (rpi > H / (2 * FS_MIN_RUN)) rpi = H / (2 * FS_MIN_RUN);         // a run re-reads K - 1 halo rows: at least 48 rows long
-    if (rpi < 1) rpi = 1;
-    const int run = (H + rpi - 1) / rpi;
-    rpi = (H + run - 1) / run;
-    const int blocks = N * rpi * sg;
-    if (!force && (H < 2 * FS_MIN_RUN || blocks < 384)) return false;
+    const RsGridPlan pl = rs_grid_plan(N, H, strips, RS_WAVES, 512, 2 * FS_MIN_RUN, 384);          // a run re-reads K - 1 halo rows: at least 48 rows long
+    if (!force && !pl.taken) return false;
 #define FV_LAUNCH(KK)                                                                                                                                          \
-    do {                                                                                                                                                      \
-        tcct_launch<k_conv32_fwdk1_stream<KK>, 80 * 1024>(dim3((unsigned)blocks), dim3(64 * nw), (size_t)KK * 2048 + (size_t)nw * FV_R * 2048 + 128, st, (const bf16*)x, \
-                           (const bf16*)wp, bias, (bf16*)y, N, H, W, strips, run, rpi);                                                                     \
-    } while (0)
+    tcct_launch<k_conv32_fwdk1_stream<KK>, RS_LDS_2PER_CU>(dim3((unsigned)pl.blocks), dim3(FS_T), fv_lds(KK).bytes, st, (const bf16*)x, (const bf16*)wp, bias, (bf16*)y, N, H, W, \
+                                                           strips, pl.run, pl.rpi)
     if (K == 13) FV_LAUNCH(13);
     else if (K == 11) FV_LAUNCH(11);
     else if (K == 9) FV_LAUNCH(9);
@@ -1970,23 +1719,14 @@ k_conv32_wgrad_line(const bf16* __restrict__ x, const bf16* __restrict__ dy, flo
         if (tg == 0) line_phase<K, 0, TPW>(acc, bsum, xl0, dl0, hh);
         else line_phase<K, TPW, K - TPW>(acc, bsum, xl0, dl0, hh);
     }
-    // the two line-group waves of a tap group hold partial sums of the same taps: they take turns in LDS (as in k_conv32_wgrad)
+    // the two line-group waves of a tap group hold partial sums of the same taps
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);
     for (int turn = 0; turn < 2; ++turn) {
         if (lg == turn) {
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) {
-                const int tap = tg * TPW + t;
-                if (tap < K) {
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const int co = (k & 3) + 8 * (k >> 2) + 4 * hh;
-                        float* dst = &red[tap * 1024 + co * 32 + r];
-                        *dst = turn == 0 ? acc[t][k] : *dst + acc[t][k];
-                    }
-                }
-            }
+            for (int t = 0; t < TPW; ++t)
+                if (tg * TPW + t < K) rs_wgrad_put(red, tg * TPW + t, acc[t], turn == 0, r, hh);
         }
         __syncthreads();
     }
@@ -1995,7 +1735,7 @@ k_conv32_wgrad_line(const bf16* __restrict__ x, const bf16* __restrict__ dy, flo
         atomicAdd(&dw[(int64_t)cc * K + tap], red[tap * 1024 + cc]);
     }
     if (dbias && tg == 0) {
-        bsum += __shfl_xor(bsum, 32, 64);
+        bsum = rs_bsum_fold(bsum);
         if (lane < 32) atomicAdd(&dbias[r], bsum);
     }
 }
@@ -2009,25 +1749,23 @@ k_conv32_wgrad_line(const bf16* __restrict__ x, const bf16* __restrict__ dy, flo
 //   K x 1: ring row = 16 x pixels + 16 dy pixels (two DMA pieces); x row b meets the dy fragments of rows b - t + (K - 1) / 2, kept in a register window
 //          of the last K dy rows (K x 4 registers), body unrolled K-fold so that window positions are compile-time; ring slot by run-time index.
 // WK_R = 8 ring rows per wave, WK_P = 6 of them in flight (one wave per SIMD has nobody to hide its latency behind: the depth does; 12 / 18 rows measured no faster,
-// DESIGN 3b, and 150 KB of LDS per block would keep the other streams' kernels off the CU).  The counted `s_waitcnt vmcnt(NPIECE * (WK_P - 1))` and the slot
-// arithmetic rest on these two constants; the launch sizes the ring from WK_R.  Same products and fp32 accumulation as the other weight-gradient kernels, summed in
+// DESIGN 3b, and 150 KB of LDS per block would keep the other streams' kernels off the CU).  The counted wait and the slot arithmetic rest on these two
+// constants (row_stream_plan.h); kernel and launch size the LDS from wk_lds_bytes.  Same products and fp32 accumulation as the other weight-gradient kernels, summed in
 // another order: bit-compatible up to that (tests/test_kernels_gpu.py).
 #define WK_T 256
-constexpr int WK_R = 8, WK_P = 6;           // ring rows per wave / rows in flight (64 / 88 KB of LDS per block)
-static_assert(WK_P <= WK_R - 2, "k_conv32_wgradk_stream: two ring slots stay free (the row being read and the one being issued into)");
 template <int K, bool VERT>
 __global__ void __launch_bounds__(WK_T, 1)
 k_conv32_wgradk_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, float* __restrict__ dw, float* __restrict__ dbias,
                        int N, int H, int W, int strips, int run) {
+    static_assert(rs_ring_ok(WK_R, WK_P) && WK_T == 64 * RS_WAVES && wk_lds_bytes(K, VERT) <= RS_LDS_1PER_CU, "k_conv32_wgradk_stream: ring invariant / LDS cap");
     constexpr int PAD = (K - 1) / 2;
-    constexpr int XP = VERT ? 16 : 16 + K - 1;                  // x pixels per ring row
-    constexpr int ROWB = (XP + 16) * 64;
+    constexpr int XP = wk_xpix(K, VERT);                        // x pixels per ring row
+    constexpr int ROWB = wk_rowb(K, VERT);
     constexpr int NPIECE = VERT ? 2 : 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, hh = lane >> 5;
     unsigned char* ring = smem + wave * (WK_R * ROWB);
-    const uint32_t ring_lds = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)ring);
+    const uint32_t ring_lds = rs_ring_lds(ring);
     const unsigned char* xb = tr_lane_base(ring, lane);
     f32x16 acc[K];
 #pragma unroll
@@ -2043,21 +1781,17 @@ k_conv32_wgradk_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, 
     const uint32_t rowb = (uint32_t)W * 64u;
     const int px = lane >> 2, c = lane & 3;
     while (cur < end) {
-        const int sidx = (int)(cur / H), r0 = (int)(cur - (int64_t)sidx * H);
-        const int n = sidx / sgroups, s = (sidx - n * sgroups) * 4 + wave;
-        const int left = (int)(end - cur);
-        const int L = __builtin_amdgcn_readfirstlane(H - r0 < left ? H - r0 : left);      // dy rows r0 .. r0 + L - 1
-        if (s >= strips) { cur += L; continue; }
-        const int w0 = s * 16;
+        const RsSeg seg = rs_run_segment(cur, end, H, sgroups, RS_WAVES, wave);
+        const int n = seg.n, r0 = seg.r0, L = seg.L;                // dy rows r0 .. r0 + L - 1
+        if (seg.s >= strips) { cur += L; continue; }
+        const int w0 = seg.s * 16;
         const u32x4 rx = make_rsrc_words(x + (int64_t)n * H * W * 32, img_bytes);
         const u32x4 rd = make_rsrc_words(dy + (int64_t)n * H * W * 32, img_bytes);
-        const int cd = w0 + px;
-        const uint32_t od = (cd < W) ? (uint32_t)(cd * 64 + c * 16) : OOB_OFF;
+        const uint32_t od = rs_col_off(w0 + px, W, 64, c * 16);
         if constexpr (!VERT) {
             // ring x pixel i <-> image column w0 - PAD + i; tap t pairs dy pixel j with x pixel j + t
-            const int cx1 = w0 - PAD + px, cx2 = cx1 + 16;
-            const uint32_t ox1 = (cx1 >= 0 && cx1 < W) ? (uint32_t)(cx1 * 64 + c * 16) : OOB_OFF;
-            const uint32_t ox2 = (px < XP - 16 && cx2 >= 0 && cx2 < W) ? (uint32_t)(cx2 * 64 + c * 16) : OOB_OFF;
+            const uint32_t ox1 = rs_col_off(w0 - PAD + px, W, 64, c * 16);
+            const uint32_t ox2 = px < XP - 16 ? rs_col_off(w0 - PAD + 16 + px, W, 64, c * 16) : OOB_OFF;
             const uint32_t row0 = (uint32_t)r0 * rowb;
             auto issue = [&](int a, int slot) {
                 const uint32_t ro = row0 + (uint32_t)a * rowb;
@@ -2074,7 +1808,7 @@ k_conv32_wgradk_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, 
 #pragma unroll
                 for (int j = 0; j < WK_R; ++j) {
                     const int a = g * WK_R + j;
-                    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPIECE * (WK_P - 1)) : "memory");         // row a has landed
+                    rs_wait_row<NPIECE, WK_P>();                        // row a has landed
                     const unsigned char* row = xb + j * ROWB;
                     const bf16x8 D = tr_load8p(row + XP * 64);
                     bf16x8 X0 = tr_load8p(row), X1 = tr_load8p(row + 64);
@@ -2093,8 +1827,7 @@ k_conv32_wgradk_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, 
             }
         } else {
             // x halo row a of the segment = image row r0 - PAD + a (a = 0 .. L + K - 2); dy row a = image row r0 + a rides in the same ring row
-            const int cx = w0 + px;
-            const uint32_t ox = (cx < W) ? (uint32_t)(cx * 64 + c * 16) : OOB_OFF;
+            const uint32_t ox = od;                             // the x pixels are the dy pixels' columns
             const int nh = L + K - 1;
             int slot_i = 0, slot_d = WK_P % WK_R;
             auto issue = [&](int a, int slot) {
@@ -2116,7 +1849,7 @@ k_conv32_wgradk_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, 
 #pragma unroll
                 for (int j = 0; j < K; ++j) {
                     const int a = g * K + j;
-                    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPIECE * (WK_P - 1)) : "memory");
+                    rs_wait_row<NPIECE, WK_P>();
                     const unsigned char* row = xb + slot_i * ROWB;
                     const bf16x8 X = tr_load8p(row);
                     Dw[j] = tr_load8p(row + 1024);                      // dy row a (zeros behind the segment)
@@ -2132,22 +1865,16 @@ k_conv32_wgradk_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, 
                 }
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        rs_wait_all();
         cur += L;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    rs_wait_all();
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);                    // [K][32 co][32 ci]
-    for (int turn = 0; turn < WK_T / 64; ++turn) {
+    for (int turn = 0; turn < RS_WAVES; ++turn) {
         if (wave == turn) {
 #pragma unroll
-            for (int t = 0; t < K; ++t)
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const int co = (k & 3) + 8 * (k >> 2) + 4 * hh;
-                    float* dst = &red[t * 1024 + co * 32 + r];
-                    *dst = turn == 0 ? acc[t][k] : *dst + acc[t][k];
-                }
+            for (int t = 0; t < K; ++t) rs_wgrad_put(red, t, acc[t], turn == 0, lane & 31, lane >> 5);
         }
         __syncthreads();
     }
@@ -2157,8 +1884,8 @@ k_conv32_wgradk_stream(const bf16* __restrict__ x, const bf16* __restrict__ dy, 
     }
     __syncthreads();
     if (dbias) {
-        bsum += __shfl_xor(bsum, 32, 64);
-        if (lane < 32) red[wave * 32 + r] = bsum;
+        bsum = rs_bsum_fold(bsum);
+        if (lane < 32) red[wave * 32 + lane] = bsum;
         __syncthreads();
         if (tid < 32) atomicAdd(&dbias[tid], red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid]);
     }
@@ -2218,18 +1945,14 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
         if (dbias && !tcct_skip_zero_fill() && hipMemsetAsync(dbias, 0, sizeof(float) * 32, st) != hipSuccess) { tcct_set_error("conv32_wgrad: memset failed"); return -2; }
     }
     if (g_wgrad_mode < 0) (void)tcct_conv32_wgrad_mode(-1);
-    constexpr int stream_on = 1;
     const int m33 = g_wgrad_mode >= 3 ? 0 : g_wgrad_mode;           // modes 3 / 4 only concern the cross convolutions
-    if ((m33 == 2 || (m33 == 0 && stream_on)) && sq && ldi == 32 && o_off == 0 && i_off == 0 && xo == 0 && dof == 0) {
+    if ((m33 == 2 || m33 == 0) && sq && ldi == 32 && o_off == 0 && i_off == 0 && xo == 0 && dof == 0) {
         const int strips = (W + 15) / 16;
         const int64_t rows = (int64_t)N * ((strips + 3) / 4) * H;            // rows of strip groups (four adjacent strips, one per wave of a block)
-        int blocks = 512;
-        int64_t run = (rows + blocks - 1) / blocks;
-        if (m33 == 2 || run >= WS_MIN_RUN) {
-            if (run < 12) run = 12;                 // small maps: fewer, longer runs (the pipeline fill is 7 rows)
-            blocks = (int)((rows + run - 1) / run);
-            constexpr size_t ldss = (size_t)(WS_T / 64) * WS_R * WS_ROWB;
-            tcct_launch<k_conv32_wgrad33_stream<false>, 80 * 1024>(dim3((unsigned)blocks), dim3(WS_T), ldss, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run);
+        const RsRunPlan pl = rs_run_plan(rows, 512, WS_MIN_RUN, 12, m33 == 2);          // floor 12: the pipeline fill is 7 rows
+        if (pl.taken) {
+            tcct_launch<k_conv32_wgrad33_stream<false>, RS_LDS_2PER_CU>(dim3((unsigned)pl.blocks), dim3(WS_T), ws_lds_bytes(), st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W,
+                                                                        strips, (int)pl.run);
             tcct_census_hit(TCCT_CENSUS_WGRAD33_STREAM);
             TCCT_LAUNCH_OK();
         }
@@ -2246,17 +1969,11 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
         xo == 0 && dof == 0) {
         const int strips = (W + 15) / 16;
         const int64_t rows = (int64_t)N * ((strips + 3) / 4) * H;
-        int blocks = 256;                           // one block (four waves, one per SIMD) per CU
-        int64_t run = (rows + blocks - 1) / blocks;
-        if (g_wgrad_mode == 3 || run >= 96) {
-            if (run < 16) run = 16;
-            blocks = (int)((rows + run - 1) / run);
+        const RsRunPlan pl = rs_run_plan(rows, 256, 96, 16, g_wgrad_mode == 3);         // 256: one block (four waves, one per SIMD) per CU
+        if (pl.taken) {
 #define WK_LAUNCH(KK, V)                                                                                                     \
-    do {                                                                                                                    \
-        constexpr size_t ring = (size_t)(WK_T / 64) * WK_R * ((V ? 16 : 16 + KK - 1) + 16) * 64, redb = (size_t)KK * 4096;                                     \
-        constexpr size_t ldsk = ring > redb ? ring : redb;                                                                                                     \
-        tcct_launch<k_conv32_wgradk_stream<KK, V>, 160 * 1024>(dim3((unsigned)blocks), dim3(WK_T), ldsk, st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, strips, (int)run); \
-    } while (0)
+    tcct_launch<k_conv32_wgradk_stream<KK, V>, RS_LDS_1PER_CU>(dim3((unsigned)pl.blocks), dim3(WK_T), wk_lds_bytes(KK, V), st, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W, \
+                                                               strips, (int)pl.run)
             if (TAPS == 13) { if (vert) WK_LAUNCH(13, true); else WK_LAUNCH(13, false); }
             else { if (vert) WK_LAUNCH(11, true); else WK_LAUNCH(11, false); }
 #undef WK_LAUNCH
@@ -2264,8 +1981,7 @@ static int conv32_wgrad_impl(const void* x, const void* dy, float* dw, float* db
             TCCT_LAUNCH_OK();
         }
     }
-    constexpr bool line_on = true;
-    if (line_on && g_wgrad_mode != 1 && (KH == 1 || KW == 1) && (TAPS == 13 || TAPS == 11 || TAPS == 9) && xs == 32 && ds == 32 && ldi == 32 && o_off == 0 && i_off == 0 &&
+    if (g_wgrad_mode != 1 && (KH == 1 || KW == 1) && (TAPS == 13 || TAPS == 11 || TAPS == 9) && xs == 32 && ds == 32 && ldi == 32 && o_off == 0 && i_off == 0 &&
         xo == 0 && dof == 0) {      // 1 x K / K x 1 at levels 0-2: shifted lines
 #define WL_LAUNCH(KK, V)                                                                                                     \
     do {                                                                                                                    \
@@ -2343,15 +2059,10 @@ extern "C" int tcct_conv32x64_wgrad33(const void* x, const void* dy, float* dw, 
     if (force || m33 != 1) {
         const int strips = (W + 15) / 16;
         const int64_t rows = (int64_t)N * ((strips + 1) / 2) * H;            // rows of strip groups (two adjacent strips, one wave pair each)
-        int blocks = 512;
-        int64_t run = (rows + blocks - 1) / blocks;
-        if (force || m33 == 2 || run >= WS_MIN_RUN) {
-            if (run < 12) run = 12;
-            blocks = (int)((rows + run - 1) / run);
-            constexpr size_t ldss = (size_t)(WS_T / 64) * WS_R * WS_ROWB;
-            static_assert(ldss >= 2 * 9 * 4096, "k_conv32_wgrad33_stream<true>: the two reduction images live in the rings");
-            tcct_launch<k_conv32_wgrad33_stream<true>, 80 * 1024>(dim3((unsigned)blocks), dim3(WS_T), ldss, (hipStream_t)stream, (const bf16*)x, (const bf16*)dy, dw, dbias, N, H, W,
-                                                                  strips, (int)run);
+        const RsRunPlan pl = rs_run_plan(rows, 512, WS_MIN_RUN, 12, force || m33 == 2);
+        if (pl.taken) {
+            tcct_launch<k_conv32_wgrad33_stream<true>, RS_LDS_2PER_CU>(dim3((unsigned)pl.blocks), dim3(WS_T), ws_lds_bytes(), (hipStream_t)stream, (const bf16*)x, (const bf16*)dy, dw,
+                                                                       dbias, N, H, W, strips, (int)pl.run);
             tcct_census_hit(TCCT_CENSUS_WGRAD33_STREAM);
             TCCT_LAUNCH_OK();
         }
@@ -2583,17 +2294,8 @@ k_conv32_bwd33(const bf16* __restrict__ x, const bf16* __restrict__ dy, const bf
     for (int turn = 0; turn < 2; ++turn) {
         if (wave >= 4 && wi == turn) {
 #pragma unroll
-            for (int t = 0; t < 5; ++t) {
-                const int tap = tap0 + t;
-                if (tap < 9) {
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const int co = (k & 3) + 8 * (k >> 2) + 4 * hh;
-                        float* dst = &red[tap * 1024 + co * 32 + r];
-                        *dst = turn == 0 ? accw[t][k] : *dst + accw[t][k];
-                    }
-                }
-            }
+            for (int t = 0; t < 5; ++t)
+                if (tap0 + t < 9) rs_wgrad_put(red, tap0 + t, accw[t], turn == 0, r, hh);
         }
         __syncthreads();
     }
@@ -2602,7 +2304,7 @@ k_conv32_bwd33(const bf16* __restrict__ x, const bf16* __restrict__ dy, const bf
         atomicAdd(&dw[(int64_t)cc * 9 + tap], red[tap * 1024 + cc]);
     }
     if (dbias && wave >= 4 && tg == 0) {
-        bsum += __shfl_xor(bsum, 32, 64);
+        bsum = rs_bsum_fold(bsum);
         if (lane < 32) atomicAdd(&dbias[r], bsum);
     }
 }
