@@ -714,6 +714,28 @@ int tcct_layout_marginals(const void* logits, int kind, int B, int H, int W, int
  * n_col.  Annotated columns as tcct_eval_layout_scores: x < w_valid and bnd_lab[b][0][x] < h_valid.  One block per image, fp64, a fixed reduction order. */
 int tcct_eval_soft_scores(const float* surf, const float* var, const int32_t* bnd_lab, int B, int S, int W, int h_valid, int w_valid, double* table,
                           tcct_stream_t stream);
+/* Layout likelihood loss (layout_loss.hip; ops.layout_nll): the negative log-likelihood of a label under the column model of tcct_layout_marginals.
+ * logits, kind, layers, S, free_mask, tau, the valid region and every limit are tcct_layout_marginals'; s, p, p~, E, gamma, post and logz are its quantities.
+ * t uint8 [B,H,W] and bnd_lab int32 [B,S-1,W] are mask and bnd of tcct_layout_decode of the label (kind 2) under the same layout: t(y,x) is the class the
+ * label's state sequence shows.  A column is annotated when x < w_valid and bnd_lab[b][0][x] < h_valid (tcct_eval_layout_scores' rule).  Per annotated column
+ *   nll(b,x) = logz(b,x) - sum_{y < h_valid} log p~(y, t(y))        >= 0: the label's (state sequence, shown classes) pair is one term of exp(logz)
+ * and 0 for every other column.  A byte of t that names no class of 0..C-1 counts as log p~ = 0 and has no one-hot entry.
+ * tcct_layout_nll_fwd is the downward walk: nll fp32 [B,W] (every element is written, 0 for a column that is not annotated or not valid) and the workspace
+ * the upward walk reads; both logarithms of a row are fp32, their sums fp64.  tcct_layout_nll_bwd is the upward walk over the same logits, t, bnd_lab and the
+ * workspace of the forward call: grad [B,H,W,C] in the dtype of the logits,
+ *   grad(y,c) = gscale k(c) (a(c) - p(c) sum_c' a(c')) / tau,   a(c) = [p(c) >= 2^-40] (post(y,c) - [c = t(y)]),   k(c) = [-1024 < logit(c) < 1024]
+ * the exact derivative of nll ((post - onehot(t)) / tau where neither floor nor clamp is active); every element is written, 0 outside the valid region and in
+ * columns that are not annotated.  gscale: a DEVICE pointer to one float (grad_output / N), read by the kernel.  No atomics: two calls give the same bits.
+ * ws: tcct_layout_nll_ws_bytes(B,H,W,S,n_free) bytes, written by _fwd and read by _bwd.  Bad arguments are refused with the outputs left as they were;
+ * h_valid == 0 or w_valid == 0 zeroes the output without a launch.
+ * tcct_layout_nll_reduce: out fp32 [2] = {sum nll / N, 1 / N} with N = h_valid x the number of annotated columns of the batch, both 0 when N = 0; one block,
+ * fp64, a fixed reduction order. */
+int64_t tcct_layout_nll_ws_bytes(int B, int H, int W, int S, int n_free);
+int tcct_layout_nll_fwd(const void* logits, int kind, const uint8_t* t, const int32_t* bnd_lab, int B, int H, int W, int C, const int* layers, int S, int free_mask,
+                        int h_valid, int w_valid, float tau, void* ws, float* nll, tcct_stream_t stream);
+int tcct_layout_nll_bwd(const void* logits, int kind, const uint8_t* t, const int32_t* bnd_lab, int B, int H, int W, int C, const int* layers, int S, int free_mask,
+                        int h_valid, int w_valid, float tau, const void* ws, const float* gscale, void* grad, tcct_stream_t stream);
+int tcct_layout_nll_reduce(const float* nll, const int32_t* bnd_lab, int B, int S, int W, int h_valid, int w_valid, float* out, tcct_stream_t stream);
 
 /* ---- boundary-regression loss pieces (RegNet.regular_reg, nets/reg.py:109-156); this pipeline is fp32 -------- */
 int tcct_slice_channels_fwd(const void* x, float* y, int64_t M, int C, int start, int n, int dtype, tcct_stream_t stream);

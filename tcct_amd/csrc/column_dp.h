@@ -1,4 +1,5 @@
-// What the column dynamic programmes share (DESIGN 6c ordered decode, 6d layout decode, 6e layout marginals) and the block sum of their score kernels.
+// What the column dynamic programmes share (DESIGN 6c ordered decode, 6d layout decode, 6e layout marginals, 6f layout likelihood loss) and the block sum of
+// their score kernels.  What only the two sum-product files share (6e, 6f) is in column_marg.h.
 //
 // The layout contract.  A LAYOUT is a top-to-bottom sequence of S states (2..16), each with a class of 0..C-1; adjacent states differ, a class may come back.
 // The classes of `free_mask` are no layer and may show inside any state; every class is a layer or free, never both.  The kernels see the layout padded:

@@ -24,67 +24,12 @@
 // through), free slots >= n_free re-read the last free class with weight 0.  The softmax denominator counts every class once: the first state of a class and
 // every real free slot.  surf, m2 and logz are accumulated per lane in fp64 (m2 - surf^2 cancels); everything else is fp32.  No atomics: two calls give the
 // same bits.
-#include "column_dp.h"
+#include "column_marg.h"
 
-#define MARG_FLOOR 9.094947017729282e-13f      // 2^-40
 // rows per batch, both walks; halved where the posterior or 14 free slots fill the registers (the emissions of a whole batch are computed ahead of its chain)
 template <int MAXS, int NF, bool POST> struct MargCfg {
     static constexpr int R = POST && NF > 2 ? (MAXS <= 10 ? 2 : 1) : (MAXS <= 8 ? 8 : 4) / (POST || NF > 2 ? 2 : 1);
 };
-
-// the loaded bits as they are: a bf16 value is widened where it is used, not where it is loaded, so that a batch of loads needs no wait of its own
-template <int MAXS, int NF> struct MargRow {
-    uint32_t z[MAXS];               // the logit of every state's class
-    uint32_t zf[NF ? NF : 1];       // ... of every free slot
-};
-__device__ __forceinline__ uint32_t marg_ldraw(const float* p) { return __float_as_uint(*p); }
-__device__ __forceinline__ uint32_t marg_ldraw(const bf16* p) { return (uint32_t)*(const uint16_t*)p; }
-template <int KIND> __device__ __forceinline__ float marg_val(uint32_t raw) { return __uint_as_float(KIND == 1 ? raw << 16 : raw); }
-// p~ of every state's class (pl), of every free slot (pf, 0 for a padded slot) and the emissions (0 for a padded state)
-template <int MAXS, int KIND, int NF>
-__device__ __forceinline__ void marg_emissions(const MargRow<MAXS, NF>& rw, float inv_tau, int first_mask, int S, int n_free, float (&E)[MAXS], float (&pl)[MAXS],
-                                               float (&pf)[NF ? NF : 1]) {
-    float t[MAXS], tf[NF ? NF : 1], mx;
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s) {
-        t[s] = column_clamp(marg_val<KIND>(rw.z[s])) * inv_tau;
-        mx = s == 0 ? t[0] : fmaxf(mx, t[s]);
-    }
-    if constexpr (NF > 0) {
-#pragma unroll
-        for (int j = 0; j < NF; ++j) {
-            tf[j] = column_clamp(marg_val<KIND>(rw.zf[j])) * inv_tau;
-            mx = fmaxf(mx, tf[j]);
-        }
-    }
-    float den = 0.f;
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s) {
-        t[s] = expf(t[s] - mx);
-        den += ((first_mask >> s) & 1) ? t[s] : 0.f;
-    }
-    if constexpr (NF > 0) {
-#pragma unroll
-        for (int j = 0; j < NF; ++j) {
-            tf[j] = expf(tf[j] - mx);
-            den += j < n_free ? tf[j] : 0.f;
-        }
-    }
-    const float inv = 1.f / den;            // den >= 1: the class of the maximum counts once
-    float F = 0.f;
-    if constexpr (NF > 0) {
-#pragma unroll
-        for (int j = 0; j < NF; ++j) {
-            pf[j] = j < n_free ? fmaxf(tf[j] * inv, MARG_FLOOR) : 0.f;
-            F += pf[j];
-        }
-    } else pf[0] = 0.f;
-#pragma unroll
-    for (int s = 0; s < MAXS; ++s) {
-        pl[s] = fmaxf(t[s] * inv, MARG_FLOOR);
-        E[s] = s < S ? pl[s] + F : 0.f;
-    }
-}
 
 // KIND: 0 fp32 logits, 1 bf16 logits.  NF: free-class slots (0: the layout has none).  POST: the per-pixel class posterior is written
 template <int MAXS, int KIND, int NF, bool POST>
@@ -145,7 +90,7 @@ __global__ void __launch_bounds__(64) k_layout_marginals(const void* __restrict_
             const float raw = ldexpf(rm[s], rk[s]);
             if (!(raw < 1.f) || s >= S) { rm[s] = 0.5f; rk[s] = 1; }       // rho <= 1 (rounding may say otherwise); a padded state passes everything through
             rho[s] = s < S ? fminf(raw, 1.f) : 1.f;
-            wcol[((int64_t)y * NV + s - 1) * W] = rho[s] < 0.5f ? rho[s] : -u;
+            wcol[((int64_t)y * NV + s - 1) * W] = marg_ws_pack(rho[s], u);
         }
         lz += (double)logf(N[MAXS - 1]);
     };
@@ -201,12 +146,7 @@ __global__ void __launch_bounds__(64) k_layout_marginals(const void* __restrict_
         u[0] = 1.f;
         rh[0] = 0.f;
 #pragma unroll
-        for (int s = 1; s < MAXS; ++s) {
-            const float v = bk.v[s - 1];
-            const bool is_u = __float_as_int(v) < 0;
-            u[s] = is_u ? -v : 1.f - v;
-            rh[s] = is_u ? 1.f + v : v;
-        }
+        for (int s = 1; s < MAXS; ++s) marg_ws_unpack(bk.v[s - 1], u[s], rh[s]);
         float Q = g[MAXS - 1], tot;
         gam[MAXS - 1] = u[MAXS - 1] * Q;
         tot = gam[MAXS - 1];
@@ -309,17 +249,9 @@ extern "C" int64_t tcct_layout_marginals_ws_bytes(int B, int H, int W, int S, in
 
 extern "C" int tcct_layout_marginals(const void* logits, int kind, int B, int H, int W, int C, const int* layers, int S, int free_mask, int h_valid, int w_valid,
                                      float tau, void* ws, float* surf, float* var, float* logz, float* post, tcct_stream_t stream) {
-    TCCT_CHECK(B >= 1 && H >= 1 && W >= 1, "layout_marginals: empty tensor");
-    TCCT_CHECK(B <= 65535, "layout_marginals: B=%d images in one call (at most 65535)", B);
-    TCCT_CHECK(C >= 2 && C <= 16, "layout_marginals: C=%d unsupported (2..16)", C);
-    TCCT_CHECK(kind == 0 || kind == 1, "layout_marginals: kind=%d (0 fp32 logits, 1 bf16 logits; a class map has no marginals)", kind);
-    TCCT_CHECK(S >= 2 && S <= 16 && layers, "layout_marginals: S=%d states (2..16)", S);
-    TCCT_CHECK(free_mask >= 0 && free_mask < (1 << C), "layout_marginals: free_mask=0x%x names a class outside 0..%d", free_mask, C - 1);
-    TCCT_CHECK(tau > 0.f && tau <= 3.0e38f, "layout_marginals: tau=%g (a positive temperature)", (double)tau);
     ColumnLayout L;
     int n_free, first_mask;
-    if (column_parse_layout("layout_marginals", C, layers, S, free_mask, L, n_free, first_mask)) return -1;
-    if (column_check_limits("layout_marginals", ", as layout_decode", H, W, C, h_valid, w_valid)) return -1;
+    if (marg_check_args("layout_marginals", kind, B, H, W, C, layers, S, free_mask, h_valid, w_valid, tau, L, n_free, first_mask)) return -1;
     TCCT_CHECK(logits && ws && surf && var && logz, "layout_marginals: logits, ws, surf, var and logz are required");
     hipStream_t st = (hipStream_t)stream;
     if (h_valid == 0 || w_valid == 0) {         // an empty valid region launches nothing and zeroes every output

@@ -35,6 +35,8 @@ class KiteSeg(KiteBack):
         self.best_dice = -1.0
         import os
         self.use_graph = os.environ.get('TCCT_GRAPH', '0') == '1'
+        if getattr(args, 'graph', False) and getattr(args, 'lay', False):
+            raise TcctError('--graph=true with the layout likelihood (+lay): the term runs eagerly only, its capture in a hipGraph is not offered (DESIGN 6f)')
         if self.use_graph or getattr(args, 'graph', False):
             from .. import ops
             ops.graphs_exclude_stage_fork('KiteSeg(--graph=true / TCCT_GRAPH=1)')      # before the first step: captures and the nested stage fork exclude each other
@@ -332,6 +334,12 @@ class KiteSeg(KiteBack):
             parts = dice_udh()
             if self.args.reg:
                 parts.append(('reg', self.model.regular_reg(out0, lab) * self.args.coff_reg))
+        if getattr(self.args, 'lay', False):
+            # the layout likelihood of the main head: on the current stream, under the dataset's layout when its file stores one
+            layout = getattr(self.dataset, 'layout', None)
+            tau = getattr(self.args, 'tau_lay', 1.0)
+            parts.append(('lay', self.model.regular_lay(out0, lab, layout, tau) * getattr(self.args, 'coff_lay', 1.0)))
+        self.loss_parts = dict(parts)
         losSum = parts[0][1]
         if getattr(self.args, 'epl', False):
             raise TcctError('--epl=true: RegNet.regular_epl does not exist in the reference either (loop_seg.py:167)')

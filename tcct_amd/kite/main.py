@@ -1,7 +1,8 @@
 """CLI — mirror of reference kite/main.py:18-72: the same 23 flags, `--net` resolved to a factory in `tcct_amd.nets`,
 `RegNet(net, con=args.type_udh, out_channels=...)`, `KiteSeg(...).fit(epochs)`.
 
-Additions: `--los=di+reg+fpl` shorthand (BASELINE.json) == `--los=di --reg=true --udh=true`; `--db=synth` synthetic
+Additions: `--los=di+reg+fpl` shorthand (BASELINE.json) == `--los=di --reg=true --udh=true`; `+lay` / `--lay=true` adds the layout likelihood of the main head
+(`--coff_lay`, `--tau_lay`); `--db=synth` synthetic
 GOALS-shaped generator; `--db=npz:FILE --crop=256,256` stored B-scans (tools/pack_dataset.py) cropped and augmented on the device; `--pl=true` = one process per GPU under torchrun; `--dtype=bf16|fp32` compute precision;
 `--los=d2|iou|mse` name the reference's other per-class criteria (DiceLoss(bi=True), IouLoss, nn.MSELoss; the reference's
 own `get_loss` only reaches Dice and MSE), also inside the shorthand (`--los=iou+reg+fpl`); `--los_weight=1,1,2,2,1` = the
@@ -62,6 +63,11 @@ def build_parser():
     p.add_argument('--udh', type=str2bool, default=False, help='udh loss!')
     p.add_argument('--coff_udh', type=float, default=1)
     p.add_argument('--type_udh', type=str, default='cos', choices=['cos', 'mse'])
+    p.add_argument('--lay', type=str2bool, default=False,
+                   help='layout likelihood loss of the main head (also --los=di+lay): -log P(label | layers ordered down every column), under the layout stored '
+                        'with --db=npz:FILE or classes increasing with depth (DESIGN 6f); eager steps only, not with --graph=true')
+    p.add_argument('--coff_lay', type=float, default=1.0, help='weight of the layout likelihood term (no best value has been measured)')
+    p.add_argument('--tau_lay', type=float, default=1.0, help='softmax temperature of the layout likelihood term (no best value has been measured)')
     p.add_argument('--ds', type=str2bool, default=False, help='Deep Supervision (always on, as in the reference)')
     p.add_argument('--coff_ds', type=float, default=1)
     p.add_argument('--pl', type=str2bool, default=False, help='Parallel: one process per GPU (torchrun)')
@@ -97,6 +103,8 @@ def parse_args(argv=None):
                 args.reg = True
             elif q in ('fpl', 'udh'):
                 args.udh = True
+            elif q == 'lay':
+                args.lay = True
             else:
                 raise SystemExit(f'unknown loss component {q!r} in --los')
     if args.legacy_heads and args.net not in ('stc_tt', 'tcct'):

@@ -94,6 +94,17 @@ class RegNet(nn.Module):
             self.tgt_list = [self.fcp.choice(pro[i], i) for i in range(pro.shape[0])]
         return los
 
+    # ------------------------------------------------------------------ layout likelihood (no counterpart in the reference)
+    def regular_lay(self, pred, true, layout=None, tau=1.0):
+        """-log P(label | the layers are ordered down every column) of `ops.layout_nll`, the training counterpart of `--decode=ordered` / `--soft`.
+        pred / true as `regular_reg` takes them; layout: an `evalm.Layout`, default classes increasing with depth."""
+        lab = as_label_index(true)
+        logits = as_nhwc(pred)
+        if layout is None:
+            from ..evalm import Layout
+            layout = Layout.identity(logits.shape[-1])
+        return ops.layout_nll(logits, lab, layout, None, tau)
+
     # ------------------------------------------------------------------ boundary regression (reference reg.py:109-156)
     def _lap_reg(self, x):
         x = ops.dwconv3x3(x, self.lap_reg[0].weight, self.lap_reg[0].bias)

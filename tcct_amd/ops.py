@@ -3668,3 +3668,79 @@ def fpl(feat, logits, labels, buf_grad, allow_lazy=True):
     """regular_udh: feat NHWC [N,H,W,32], logits NHWC [N,H,W,C] (no grad flows to them), labels uint8 [N,H,W],
     buf_grad fp32 [C,32] -> (loss, prototypes [C,32,32]).  allow_lazy=False (or a watched `feat`): the gradient wrt feat is the dense tensor."""
     return _Fpl.apply(feat, logits.detach(), labels, buf_grad, bool(allow_lazy) and not grad_is_watched(feat))
+
+
+# ---------------------------------------------------------------------------------------------------------------- layout likelihood loss (DESIGN 6f)
+_LAYOUT_LABEL_CACHE = {}
+
+
+def layout_label(labels_u8, layout, valid=None):
+    """(t uint8 [B,H,W], bnd_lab int32 [B,S-1,W]) = mask and surfaces of `evalm.layout_decode` of the label under `layout`: the nearest label the layout can
+    produce, what the evaluator scores against.  One-entry cache per label tensor, with the rules of `nets.reg.as_label_index`."""
+    from . import evalm
+    key = (labels_u8.data_ptr(), tuple(labels_u8.shape), labels_u8._version, layout, valid)
+    hit = _LAYOUT_LABEL_CACHE.get('k')
+    if hit is not None and hit[0] == key and hit[2]() is labels_u8:
+        return hit[1]
+    t, bnd = evalm.layout_decode(labels_u8, layout, valid)[:2]
+    _LAYOUT_LABEL_CACHE['k'] = (key, (t, bnd), weakref.ref(labels_u8))
+    return t, bnd
+
+
+class _LayoutNll(_FastFunction):
+    @staticmethod
+    def forward(ctx, logits, t, bnd, layout, hv, wv, tau):
+        B, H, W, C = logits.shape
+        S, dev = layout.n_states, logits.device
+        nbytes = lib.layout_nll_ws_bytes(B, H, W, S, len(layout.free))
+        if nbytes < 0:
+            raise TcctError(f'tcct_layout_nll_ws_bytes failed: {lib.last_error()}')
+        ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)              # lives until backward: the upward walk reads what the downward walk left
+        nll = torch.empty((B, W), device=dev, dtype=torch.float32)
+        out = torch.empty((2,), device=dev, dtype=torch.float32)               # loss, 1 / N: both formed on the device
+        kind = dtype_code(logits.dtype)
+        lib.layout_nll_fwd(logits, kind, t, bnd, B, H, W, C, layout._c_layers, S, layout.free_mask, hv, wv, tau, ws, nll)
+        lib.layout_nll_reduce(nll, bnd, B, S, W, hv, wv, out)
+        ctx.save_for_backward(logits, t, bnd, ws, out)
+        ctx.cfg = (layout, hv, wv, tau)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, t, bnd, ws, out = ctx.saved_tensors
+        layout, hv, wv, tau = ctx.cfg
+        B, H, W, C = logits.shape
+        gscale = (_as(g, torch.float32) * out[1]).reshape(1)                   # grad_output / N: one float, read by the kernel
+        grad = torch.empty_like(logits)
+        lib.layout_nll_bwd(logits, dtype_code(logits.dtype), t, bnd, B, H, W, C, layout._c_layers, layout.n_states, layout.free_mask, hv, wv, tau, ws, gscale, grad)
+        return grad, None, None, None, None, None, None
+
+
+def layout_nll(logits_nhwc, labels_u8, layout, valid=None, tau=1.0):
+    """Layout likelihood loss (layout_loss.hip): the mean over the annotated columns and their h_valid rows of -log P(label | ordered), the share the
+    label's (state sequence, shown classes) pair holds of the column's partition function of `evalm.layout_marginals`.  logits fp32 / bf16 NHWC [B,H,W,C];
+    labels uint8 [B,H,W] (they go through `evalm.layout_decode` first: a label the layout cannot produce is replaced by the nearest one it can);
+    valid = (h_valid, w_valid), default the whole image; tau > 0.  -> scalar fp32 tensor, 0 when no column is annotated; differentiable in the logits
+    (the gradient is exact, in the logits' dtype).  Eager, on the current stream, no host sync; two calls give the same bits."""
+    from . import evalm
+    if not isinstance(layout, evalm.Layout):
+        raise TcctError(f'layout_nll: layout must be an evalm.Layout, got {type(layout).__name__}')
+    try:
+        tau = float(tau)
+    except (TypeError, ValueError):
+        raise TcctError(f'layout_nll: tau={tau!r} (a positive temperature)')
+    if not 0.0 < tau < float('inf'):
+        raise TcctError(f'layout_nll: tau={tau!r} (a positive temperature)')
+    if not (torch.is_tensor(logits_nhwc) and logits_nhwc.is_cuda and torch.is_tensor(labels_u8) and labels_u8.is_cuda):
+        raise TcctError('layout_nll: logits and labels must be CUDA tensors (no CPU fallback)')
+    if logits_nhwc.dtype not in (torch.float32, torch.bfloat16):
+        raise TcctError(f'layout_nll: fp32 / bf16 logits [B,H,W,C] expected, got {logits_nhwc.dtype}')
+    C = layout.n_class
+    if logits_nhwc.dim() != 4 or logits_nhwc.shape[3] != C:
+        raise TcctError(f'layout_nll: logits {tuple(logits_nhwc.shape)} are not NHWC [B,H,W,{C}]')
+    B, H, W = logits_nhwc.shape[:3]
+    if labels_u8.dtype != torch.uint8 or tuple(labels_u8.shape) != (B, H, W):
+        raise TcctError(f'layout_nll: labels must be uint8 class indices [{B},{H},{W}], got {labels_u8.dtype}{tuple(labels_u8.shape)}')
+    hv, wv = (H, W) if valid is None else (int(valid[0]), int(valid[1]))
+    t, bnd = layout_label(labels_u8.contiguous(), layout, (hv, wv))
+    return _LayoutNll.apply(logits_nhwc.contiguous(), t, bnd, layout, hv, wv, tau)
