@@ -459,10 +459,11 @@ int tcct_stream_copy(const void* src, void* dst, int64_t nbytes, tcct_stream_t s
 /* test tooling, no reference counterpart: number of launches of kernel family `which` since the last reset (0 k_conv32_chain33, 1 k_conv32_wgradk_stream,
  * 2 k_conv32_wgrad33_stream, 3 k_conv32_fwd33_stream; the pointwise GEMMs: 4 k_pw_fwd, 5..9 k_pw_fwd with 1..5 N-tiles per block, 10 k_pw_fwd2, 11 k_pw_bwd,
  * 12 k_pw_wgrad, 13 k_pw_wgrad_smalln, 14 k_pw_wgrad_smalln_mfma, 15 k_pwf_mfma, 16 k_pwf_wgrad; the C3 first-layer launches are not counted; the depthwise 3x3 kernels: k_dw_fwd with 17 one column per thread at stride 1,
- * 18 stride 2, 19 four columns per thread, 20 k_dw_dgrad_s2, k_dw_wgrad with 21 one / 22 two columns per thread); reset != 0 clears it
+ * 18 stride 2, 19 four columns per thread, 20 k_dw_dgrad_s2, k_dw_wgrad with 21 one / 22 two columns per thread; the resize family: tcct_bilinear_bwd's 24 k_bilinear_bwd_x2, 25 k_bilinear_bwd_tab,
+ * 26 k_bilinear_bwd (candidate search), 27 tcct_bilinear_bwd_separable, tcct_normadd_fwd's 28 k_normadd_fwd_band / 29 k_normadd_fwd); reset != 0 clears it
  * after reading; -1 for an unknown family.  The entry points choose a kernel per shape:
  * tests/test_fullsize_gpu.py asserts with this that the bench-shape step was served by the row-stream / chain kernels it means to check, tests/test_pw_exact_gpu.py that
- * every pointwise case reached the kernel (and the N-tiles per block) it was derived for, tests/test_dw_exact_gpu.py the same for the depthwise kernels. */
+ * every pointwise case reached the kernel (and the N-tiles per block) it was derived for, tests/test_dw_exact_gpu.py the same for the depthwise kernels, tests/test_resize_exact_gpu.py for the resize routes. */
 int64_t tcct_kernel_census(int which, int reset);
 /* measurement tooling (tools/attrib_trace.py), no reference counterpart: an empty launch of `id` blocks x 64 threads -- the grid size is the only thing a
  * kernel trace / PMC table records about a dispatch, so a marker in front of every C-ABI call lets the tables be cut into calls; 1 <= id < 2^20 */

@@ -16,7 +16,11 @@ enum { TCCT_CENSUS_CHAIN33 = 0, TCCT_CENSUS_WGRADK_STREAM = 1, TCCT_CENSUS_WGRAD
        TCCT_CENSUS_PW_WGRAD_SMALLN = 13, TCCT_CENSUS_PW_WGRAD_SMALLN_MFMA = 14, TCCT_CENSUS_PWF_FWD = 15, TCCT_CENSUS_PWF_WGRAD = 16,
        // depthwise 3x3 (dwconv.hip): k_dw_fwd with one column per thread at stride 1 / at stride 2 / with four columns per thread, k_dw_dgrad_s2, k_dw_wgrad with one / two columns per thread
        TCCT_CENSUS_DW_FWD_S1 = 17, TCCT_CENSUS_DW_FWD_S2 = 18, TCCT_CENSUS_DW_FWD_CPT4 = 19, TCCT_CENSUS_DW_DGRAD_S2 = 20, TCCT_CENSUS_DW_WGRAD = 21,
-       TCCT_CENSUS_DW_WGRAD_CPT2 = 22, TCCT_CENSUS_N = 24 };
+       TCCT_CENSUS_DW_WGRAD_CPT2 = 22,
+       // resize family (pool_resize.hip): the routes of tcct_bilinear_bwd -- k_bilinear_bwd_x2 (lane exchange), k_bilinear_bwd_tab (table gather), k_bilinear_bwd (candidate
+       // search) --, tcct_bilinear_bwd_separable (one hit for its two passes), and tcct_normadd_fwd's k_normadd_fwd_band / k_normadd_fwd (row by row)
+       TCCT_CENSUS_BL_BWD_X2 = 24, TCCT_CENSUS_BL_BWD_TAB = 25, TCCT_CENSUS_BL_BWD_SEARCH = 26, TCCT_CENSUS_BL_BWD_SEP = 27, TCCT_CENSUS_NORMADD_BAND = 28,
+       TCCT_CENSUS_NORMADD_ROWS = 29, TCCT_CENSUS_N = 32 };
 void tcct_census_hit(int which);
 int tcct_skip_zero_fill();      // 1: the caller guarantees accumulation outputs are already zero (tcct_set_outputs_prezeroed)
 

@@ -341,8 +341,10 @@ __global__ void __launch_bounds__(PB) k_bilinear_bwd_tab(const T* __restrict__ d
             int rI[4], cI[4]; float rW[4], cW[4];
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
-                rI[a] = a < nr ? ri[a] : ri[0]; rW[a] = a < nr ? rw[a] : 0.f;
-                cI[a] = a < nc ? ci[a] : ci[0]; cW[a] = a < nc ? cw[a] : 0.f;
+                // (an input row or column NO output interpolates from -- any reduction by more than 2 -- has an empty table whose entry 0 was never written:
+                // its padding is index 0, a valid element of dy, with weight 0 like every other padding.  The arithmetic of non-empty pixels is untouched.)
+                rI[a] = a < nr ? ri[a] : (nr ? ri[0] : 0); rW[a] = a < nr ? rw[a] : 0.f;
+                cI[a] = a < nc ? ci[a] : (nc ? ci[0] : 0); cW[a] = a < nc ? cw[a] : 0.f;
             }
             float v[4][4][VEC];
 #pragma unroll
@@ -560,6 +562,7 @@ extern "C" int tcct_bilinear_bwd_separable(const float* dy, float* dx, float* wo
     const int64_t rows = (int64_t)N * Ho;
     hipLaunchKernelGGL(k_bilinear_bwd_1d<true>, dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(PB), row_bytes, st, dy, workspace, N * Ho, W, Wo, 0, C, sw, align_corners);
     hipLaunchKernelGGL(k_bilinear_bwd_1d<false>, row_grid(W * C, (int64_t)N * H), dim3(PB), 0, st, workspace, dx, N * H, H, Ho, W, C, sh, align_corners);
+    tcct_census_hit(TCCT_CENSUS_BL_BWD_SEP);        // (behind the launches: the refusals above return before it)
     TCCT_LAUNCH_OK();
 }
 
@@ -567,20 +570,21 @@ extern "C" int tcct_bilinear_bwd_separable(const float* dy, float* dx, float* wo
 // (20-byte lane stride) 0.159 ms, flat runs of four floats with 16-byte accesses for the addend and the result 0.139 ms -- the four scalar source gathers per
 // element, not the streams, are the cost; a separable two-pass form would halve them.)
 static int bilinear_fwd_impl(const void* x, const void* res, void* y, int N, int H, int W, int C, int Ho, int Wo, int align_corners,
-                             int dtype, tcct_stream_t stream);
+                             int dtype, tcct_stream_t stream, const char* who);
 extern "C" int tcct_bilinear_fwd(const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, int align_corners,
                                  int dtype, tcct_stream_t stream) {
-    return bilinear_fwd_impl(x, nullptr, y, N, H, W, C, Ho, Wo, align_corners, dtype, stream);
+    return bilinear_fwd_impl(x, nullptr, y, N, H, W, C, Ho, Wo, align_corners, dtype, stream, "bilinear_fwd");
 }
 /* y = resize(x) + res with res, y [N,Ho,Wo,C]: upsampling with the skip-connection add folded in */
 extern "C" int tcct_bilinear_add_fwd(const void* x, const void* res, void* y, int N, int H, int W, int C, int Ho, int Wo,
                                      int align_corners, int dtype, tcct_stream_t stream) {
     TCCT_CHECK(res != nullptr, "bilinear_add_fwd: res is NULL");
-    return bilinear_fwd_impl(x, res, y, N, H, W, C, Ho, Wo, align_corners, dtype, stream);
+    return bilinear_fwd_impl(x, res, y, N, H, W, C, Ho, Wo, align_corners, dtype, stream, "bilinear_add_fwd");
 }
 static int bilinear_fwd_impl(const void* x, const void* res, void* y, int N, int H, int W, int C, int Ho, int Wo, int align_corners,
-                             int dtype, tcct_stream_t stream) {
-    TCCT_CHECK(H > 0 && W > 0 && Ho > 0 && Wo > 0, "bilinear_fwd: bad sizes");
+                             int dtype, tcct_stream_t stream, const char* who) {
+    TCCT_CHECK(H > 0 && W > 0 && Ho > 0 && Wo > 0, "%s: bad sizes", who);
+    TCCT_CHECK(N >= 1 && C >= 1, "%s: N=%d C=%d", who, N, C);        // (C = 0 divides by zero in the kernel, N = 0 is a zero-sized launch)
     float sh = align_corners ? (Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f) : (float)H / (float)Ho;
     float sw = align_corners ? (Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f) : (float)W / (float)Wo;
     int vec = (C % 4 == 0) ? 4 : 1;
@@ -602,6 +606,7 @@ extern "C" int64_t tcct_bilinear_bwd_x2(int on) { const int old = g_bilinear_x2;
 extern "C" int tcct_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, int C, int Ho, int Wo, int align_corners,
                                  int dtype, tcct_stream_t stream) {
     TCCT_CHECK(H > 0 && W > 0 && Ho > 0 && Wo > 0, "bilinear_bwd: bad sizes");
+    TCCT_CHECK(N >= 1 && C >= 1, "bilinear_bwd: N=%d C=%d", N, C);
     float sh = align_corners ? (Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f) : (float)H / (float)Ho;
     float sw = align_corners ? (Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f) : (float)W / (float)Wo;
     int vec = (C % 4 == 0) ? 4 : 1;
@@ -618,6 +623,7 @@ extern "C" int tcct_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, 
             if (nch == 8) hipLaunchKernelGGL((k_bilinear_bwd_x2<bf16, 8, false>), grid, dim3(PB), 0, st, (const bf16*)dy, (bf16*)dx, N, H, W, C, wcols, hstrips);
             else if (nch == 5) hipLaunchKernelGGL((k_bilinear_bwd_x2<float, 5, true>), grid, dim3(PB), 0, st, (const float*)dy, (float*)dx, N, H, W, C, wcols, hstrips);
             else hipLaunchKernelGGL((k_bilinear_bwd_x2<float, 9, true>), grid, dim3(PB), 0, st, (const float*)dy, (float*)dx, N, H, W, C, wcols, hstrips);
+            tcct_census_hit(TCCT_CENSUS_BL_BWD_X2);
             TCCT_LAUNCH_OK();
         }
     }
@@ -633,15 +639,18 @@ extern "C" int tcct_bilinear_bwd(const void* dy, void* dx, int N, int H, int W, 
         if (v8 < 0) v8 = 1;
         if (v8 && dtype == TCCT_BF16 && C % 8 == 0) {
             hipLaunchKernelGGL((k_bilinear_bwd_tab<bf16, 8>), dim3((unsigned)blocks), dim3(PB), lds, st, (const bf16*)dy, (bf16*)dx, N, H, W, C, Ho, Wo, sh, sw, align_corners, DW, KT, tilesW, tilesH);
+            tcct_census_hit(TCCT_CENSUS_BL_BWD_TAB);
             TCCT_LAUNCH_OK();
         }
         if (vec == 4) { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_bilinear_bwd_tab<T, 4>), dim3((unsigned)blocks), dim3(PB), lds, st, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, sh, sw, align_corners, DW, KT, tilesW, tilesH)); }
         else { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_bilinear_bwd_tab<T, 1>), dim3((unsigned)blocks), dim3(PB), lds, st, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, sh, sw, align_corners, DW, KT, tilesW, tilesH)); }
+        tcct_census_hit(TCCT_CENSUS_BL_BWD_TAB);
         TCCT_LAUNCH_OK();
     }
     int64_t total = (int64_t)N * H * W * (C / vec);
     if (vec == 4) { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_bilinear_bwd<T, 4>), dim3(tcct_grid(total, PB, 1 << 16)), dim3(PB), 0, st, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, sh, sw, align_corners)); }
     else { TCCT_DISPATCH(dtype, hipLaunchKernelGGL((k_bilinear_bwd<T, 1>), dim3(tcct_grid(total, PB, 1 << 16)), dim3(PB), 0, st, (const T*)dy, (T*)dx, N, H, W, C, Ho, Wo, sh, sw, align_corners)); }
+    tcct_census_hit(TCCT_CENSUS_BL_BWD_SEARCH);
     TCCT_LAUNCH_OK();
 }
 
@@ -1106,9 +1115,11 @@ extern "C" int tcct_normadd_fwd(const void* g0, const void* g1, const void* g2, 
     if (banded < 0) banded = 1;
     if (banded && H == 2 * h1 && H == 4 * h2 && H % 8 == 0) {
         TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_normadd_fwd_band<T>, row_grid(W * LP, (int64_t)N * (H / 8), 8192), dim3(PB), 0, st, (const T*)g0, (const T*)g1, (const T*)g2, inv1, inv2, (T*)out, N, H, W, C, h1, w1, h2, w2, eps));
+        tcct_census_hit(TCCT_CENSUS_NORMADD_BAND);
         TCCT_LAUNCH_OK();
     }
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_normadd_fwd<T>, row_grid(W * LP, ((int64_t)N * H + NA_ROWS - 1) / NA_ROWS, 8192), dim3(PB), 0, st, (const T*)g0, (const T*)g1, (const T*)g2, inv1, inv2, (T*)out, N, H, W, C, h1, w1, h2, w2, eps));
+    tcct_census_hit(TCCT_CENSUS_NORMADD_ROWS);
     TCCT_LAUNCH_OK();
 }
 

@@ -212,7 +212,7 @@ def test_the_mirror_matches_the_launch_conditions_in_the_source():
         assert needle in att, needle
     com = open(os.path.join(here, '..', 'tcct_amd', 'csrc', 'common.h')).read()
     fam = dict(re.findall(r'TCCT_CENSUS_(DW_\w+) = (\d+)', com))
-    assert fam == dict(DW_FWD_S1='17', DW_FWD_S2='18', DW_FWD_CPT4='19', DW_DGRAD_S2='20', DW_WGRAD='21', DW_WGRAD_CPT2='22') and 'TCCT_CENSUS_N = 24' in com
+    assert fam == dict(DW_FWD_S1='17', DW_FWD_S2='18', DW_FWD_CPT4='19', DW_DGRAD_S2='20', DW_WGRAD='21', DW_WGRAD_CPT2='22') and 'TCCT_CENSUS_N = 32' in com
 
 
 def test_every_exact_case_tells_the_wrong_variants_apart():
