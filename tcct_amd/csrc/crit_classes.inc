@@ -209,16 +209,16 @@ __global__ void __launch_bounds__(256) k_upcrit_bwd_w(const float* __restrict__ 
     do { if (K_ == TCCT_CRIT_DICE) { constexpr int KIND = TCCT_CRIT_DICE; STMT; } else if (K_ == TCCT_CRIT_DICE2) { constexpr int KIND = TCCT_CRIT_DICE2; STMT; } \
          else if (K_ == TCCT_CRIT_IOU) { constexpr int KIND = TCCT_CRIT_IOU; STMT; } else { constexpr int KIND = TCCT_CRIT_MSE; STMT; } } while (0)
 #define CRIT_ARGS_OK(what) \
-    TCCT_CHECK(C >= 2 && C <= MAXC, what ": C=%d unsupported (2..%d)", C, MAXC); \
+    TCCT_CHECK(C >= 2 && C <= MAXC, what ": C=%d unsupported (2..16)", C); \
     TCCT_CHECK(kind >= TCCT_CRIT_DICE && kind <= TCCT_CRIT_MSE, what ": kind=%d unknown (0 dice, 1 dice2, 2 iou, 3 mse)", kind)
 
 static int crit_launch_sums(const void* logits, const uint8_t* labels, int64_t M, int C, int kind, double* sums, int dtype, hipStream_t st) {
     TCCT_DISPATCH(dtype, CRIT_KINDS(kind, hipLaunchKernelGGL((k_crit_sums<T, KIND>), dim3(tcct_grid(M, CSB, 512)), dim3(CSB), 0, st, (const T*)logits, labels, M, C, sums)));
     return 0;
 }
-static int crit_launch_upsums(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, double* sums, hipStream_t st) {
+static int crit_launch_upsums(const char* what, const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, double* sums, hipStream_t st) {
     int Sc;
-    if (int rc = upsampled_args_ok("upcrit", B, h, w, H, W, &Sc)) return rc;
+    if (int rc = upsampled_args_ok(what, B, h, w, H, W, &Sc)) return rc;
     UPDICE_SCALES(Sc, CRIT_KINDS(kind, hipLaunchKernelGGL((k_upcrit_sums<S, KIND>), dim3(tcct_grid((int64_t)B * H * w, UDB, 512)), dim3(UDB), 0, st, low, labels, B, h, w, H, W, C,
                                                           (float)h / (float)H, sums)));
     return 0;
@@ -226,7 +226,8 @@ static int crit_launch_upsums(const float* low, const uint8_t* labels, int B, in
 static int tcct_softmax_crit_fwd_impl(const void* logits, const uint8_t* labels, int64_t M, int C, int kind, const float* class_w, double* sums, float* loss, int dtype,
                                       tcct_stream_t stream) {
     CRIT_ARGS_OK("softmax_crit_fwd");
-    TCCT_CHECK(M >= 1, "softmax_crit_fwd: empty tensor");
+    TCCT_CHECK(M >= 1, "softmax_crit_fwd: M=%lld: empty tensor (M >= 1)", (long long)M);
+    LOSS_DTYPE_OK("softmax_crit_fwd");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C, st) != hipSuccess) { tcct_set_error("softmax_crit_fwd: memset failed"); return -2; }
     if (int rc = crit_launch_sums(logits, labels, M, C, kind, sums, dtype, st)) return rc;
@@ -236,7 +237,8 @@ static int tcct_softmax_crit_fwd_impl(const void* logits, const uint8_t* labels,
 static int tcct_softmax_crit_bwd_impl(const void* logits, const uint8_t* labels, int64_t M, int C, int kind, const float* class_w, const double* sums, const float* grad_out,
                                       float grad_scale, void* dlogits, int dtype, tcct_stream_t stream) {
     CRIT_ARGS_OK("softmax_crit_bwd");
-    TCCT_CHECK(M >= 1, "softmax_crit_bwd: empty tensor");
+    TCCT_CHECK(M >= 1, "softmax_crit_bwd: M=%lld: empty tensor (M >= 1)", (long long)M);
+    LOSS_DTYPE_OK("softmax_crit_bwd");
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_crit_bwd<T>, dim3(tcct_grid(M, LB, 1 << 16)), dim3(LB), 0, (hipStream_t)stream, (const T*)logits, labels, M, C, kind, class_w, sums,
                                             grad_out, grad_scale, (T*)dlogits));
     TCCT_LAUNCH_OK();
@@ -244,9 +246,11 @@ static int tcct_softmax_crit_bwd_impl(const void* logits, const uint8_t* labels,
 static int tcct_upcrit_fwd_impl(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, double* sums, float* loss,
                                 tcct_stream_t stream) {
     CRIT_ARGS_OK("upcrit_fwd");
+    int Sc;
+    if (int rc = upsampled_args_ok("upcrit_fwd", B, h, w, H, W, &Sc)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C, st) != hipSuccess) { tcct_set_error("upcrit_fwd: memset failed"); return -2; }
-    if (int rc = crit_launch_upsums(low, labels, B, h, w, H, W, C, kind, sums, st)) return rc;
+    if (int rc = crit_launch_upsums("upcrit_fwd", low, labels, B, h, w, H, W, C, kind, sums, st)) return rc;
     hipLaunchKernelGGL(k_crit_finalize, dim3(1), dim3(64), 0, st, sums, C, 1, 1.f, kind, class_w, (double)B * H * W, loss);
     TCCT_LAUNCH_OK();
 }
@@ -266,13 +270,16 @@ static int tcct_upcrit_bwd_impl(const float* low, const uint8_t* labels, int B, 
 static int tcct_crit_ds_fwd_impl(const void* logits, int dtype, const uint8_t* labels, int B, int H, int W, int C, const float* const* lows, const int* lh, const int* lw,
                                  int nlow, float coff, int kind, const float* class_w, double* sums, float* loss, tcct_stream_t stream) {
     CRIT_ARGS_OK("crit_ds_fwd");
-    TCCT_CHECK(nlow >= 0 && nlow <= 3 && B >= 1 && H >= 1 && W >= 1, "crit_ds_fwd: %d low-resolution heads (0..3), %dx%dx%d", nlow, B, H, W);
+    TCCT_CHECK(nlow >= 0 && nlow <= 3 && B >= 1 && H >= 1 && W >= 1, "crit_ds_fwd: %d low-resolution heads (0..3), %dx%dx%d (B, H, W >= 1)", nlow, B, H, W);
+    LOSS_DTYPE_OK("crit_ds_fwd");
+    for (int i = 0, Sc; i < nlow; ++i)
+        if (int rc = upsampled_args_ok("crit_ds_fwd", B, lh[i], lw[i], H, W, &Sc)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C * (1 + nlow), st) != hipSuccess) { tcct_set_error("crit_ds_fwd: memset failed"); return -2; }
     const int64_t M = (int64_t)B * H * W;
     if (int rc = crit_launch_sums(logits, labels, M, C, kind, sums, dtype, st)) return rc;
     for (int i = 0; i < nlow; ++i)
-        if (int rc = crit_launch_upsums(lows[i], labels, B, lh[i], lw[i], H, W, C, kind, sums + (size_t)(i + 1) * 3 * C, st)) return rc;
+        if (int rc = crit_launch_upsums("crit_ds_fwd", lows[i], labels, B, lh[i], lw[i], H, W, C, kind, sums + (size_t)(i + 1) * 3 * C, st)) return rc;
     hipLaunchKernelGGL(k_crit_finalize, dim3(1), dim3(64), 0, st, sums, C, 1 + nlow, coff, kind, class_w, (double)M, loss);
     TCCT_LAUNCH_OK();
 }

@@ -40,7 +40,9 @@ __global__ void k_dice_finalize(const double* __restrict__ sums, int C, float* _
 }
 static int tcct_softmax_dice_fwd_impl(const void* logits, const uint8_t* labels, int64_t M, int C, double* sums, float* loss,
                                      int dtype, tcct_stream_t stream) {
-    TCCT_CHECK(C >= 2 && C <= MAXC, "softmax_dice_fwd: C=%d unsupported (2..%d)", C, MAXC);
+    TCCT_CHECK(C >= 2 && C <= MAXC, "softmax_dice_fwd: C=%d unsupported (2..16)", C);
+    TCCT_CHECK(M >= 1, "softmax_dice_fwd: M=%lld: empty tensor (M >= 1)", (long long)M);
+    LOSS_DTYPE_OK("softmax_dice_fwd");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C, st) != hipSuccess) { tcct_set_error("softmax_dice_fwd: memset failed"); return -2; }
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_dice_sums<T>, dim3(tcct_grid(M, DSB, 512)), dim3(DSB), 0, st, (const T*)logits, labels, M, C, sums));
@@ -91,7 +93,9 @@ __global__ void k_dice_bwd(const T* __restrict__ logits, const uint8_t* __restri
 }
 static int tcct_softmax_dice_bwd_impl(const void* logits, const uint8_t* labels, int64_t M, int C, const double* sums,
                                      const float* grad_out, float grad_scale, void* dlogits, int dtype, tcct_stream_t stream) {
-    TCCT_CHECK(C >= 2 && C <= MAXC, "softmax_dice_bwd: C=%d unsupported", C);
+    TCCT_CHECK(C >= 2 && C <= MAXC, "softmax_dice_bwd: C=%d unsupported (2..16)", C);
+    TCCT_CHECK(M >= 1, "softmax_dice_bwd: M=%lld: empty tensor (M >= 1)", (long long)M);
+    LOSS_DTYPE_OK("softmax_dice_bwd");
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_dice_bwd<T>, dim3(tcct_grid(M, LB, 1 << 16)), dim3(LB), 0, (hipStream_t)stream, (const T*)logits, labels, M, C, sums, grad_out, grad_scale, (T*)dlogits));
     TCCT_LAUNCH_OK();
 }
@@ -140,7 +144,9 @@ static int dice_launch_upsums(const char* what, const float* low, const uint8_t*
 }
 static int tcct_updice_fwd_impl(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, double* sums,
                                float* loss, tcct_stream_t stream) {
-    TCCT_CHECK(C >= 2 && C <= MAXC, "updice_fwd: C=%d unsupported (2..%d)", C, MAXC);
+    TCCT_CHECK(C >= 2 && C <= MAXC, "updice_fwd: C=%d unsupported (2..16)", C);
+    int Sc;
+    if (int rc = upsampled_args_ok("updice_fwd", B, h, w, H, W, &Sc)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C, st) != hipSuccess) { tcct_set_error("updice_fwd: memset failed"); return -2; }
     if (int rc = dice_launch_upsums("updice_fwd", low, labels, B, h, w, H, W, C, sums, st)) return rc;
@@ -220,7 +226,7 @@ __global__ void __launch_bounds__(256) k_updice_bwd_w(const float* __restrict__ 
 }
 static int tcct_updice_bwd_impl(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, const double* sums,
                                const float* grad_out, float grad_scale, float* ws, float* dlow, tcct_stream_t stream) {
-    TCCT_CHECK(C >= 2 && C <= MAXC, "updice_bwd: C=%d unsupported", C);
+    TCCT_CHECK(C >= 2 && C <= MAXC, "updice_bwd: C=%d unsupported (2..16)", C);
     int Sc;
     if (int rc = upsampled_args_ok("updice_bwd", B, h, w, H, W, &Sc)) return rc;
     TCCT_CHECK(ws != nullptr, "updice_bwd: workspace [B,H,w,C] fp32 is NULL");
@@ -310,7 +316,11 @@ __global__ void k_dice_finalize_ds(const double* __restrict__ sums, int C, int n
 }
 static int tcct_dice_ds_fwd_impl(const void* logits, int dtype, const uint8_t* labels, int B, int H, int W, int C, const float* const* lows, const int* lh,
                                  const int* lw, int nlow, float coff, double* sums, float* loss, tcct_stream_t stream) {
-    TCCT_CHECK(C >= 2 && C <= MAXC && nlow >= 0 && nlow <= 3, "dice_ds_fwd: C=%d (2..%d), %d low-resolution heads (0..3)", C, MAXC, nlow);
+    TCCT_CHECK(C >= 2 && C <= MAXC && nlow >= 0 && nlow <= 3, "dice_ds_fwd: C=%d (2..16), %d low-resolution heads (0..3)", C, nlow);
+    TCCT_CHECK(B >= 1 && H >= 1 && W >= 1, "dice_ds_fwd: empty tensor %dx%dx%d (B, H, W >= 1)", B, H, W);
+    LOSS_DTYPE_OK("dice_ds_fwd");
+    for (int i = 0, Sc; i < nlow; ++i)
+        if (int rc = upsampled_args_ok("dice_ds_fwd", B, lh[i], lw[i], H, W, &Sc)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C * (1 + nlow), st) != hipSuccess) { tcct_set_error("dice_ds_fwd: memset failed"); return -2; }
     const int64_t M = (int64_t)B * H * W;

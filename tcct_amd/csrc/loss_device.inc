@@ -97,12 +97,14 @@ __device__ __forceinline__ void updice_pixel(const float (&R)[3][MAXC], int kk /
 #define UPDICE_SCALES(S_, STMT) \
     do { if (S_ == 2) { constexpr int S = 2; STMT; } else if (S_ == 4) { constexpr int S = 4; STMT; } else if (S_ == 8) { constexpr int S = 8; STMT; } \
          else { constexpr int S = 16; STMT; } } while (0)
+// every refusal of the criterion entries is made BEFORE the first access (the memset of sums included): a refused call leaves its outputs as they were
+#define LOSS_DTYPE_OK(what) TCCT_CHECK(dtype == TCCT_F32 || dtype == TCCT_BF16, what ": bad dtype %d (0 fp32, 1 bf16)", (int)dtype)
 // the argument check of every upsampled head: an integer scale 2/4/8/16 (-> *Sc) and item counts that fit the kernels' 32-bit indices
 static int upsampled_args_ok(const char* what, int B, int h, int w, int H, int W, int* Sc) {
     *Sc = h > 0 ? H / h : 0;
     TCCT_CHECK(B >= 1 && h >= 1 && w >= 1 && H == *Sc * h && W == *Sc * w && (*Sc == 2 || *Sc == 4 || *Sc == 8 || *Sc == 16),
                "%s: needs an integer scale 2/4/8/16 (got %dx%d -> %dx%d)", what, h, w, H, W);
-    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "%s: tensor too large", what);
+    TCCT_CHECK((int64_t)B * H * w < (1LL << 31), "%s: tensor too large (B * H * w = %lld, below 2^31)", what, (long long)B * H * w);
     return 0;
 }
 // pass 2: dlow[n, i, j, c] = sum_ho wh(ho, i) T[n, ho, j, c]

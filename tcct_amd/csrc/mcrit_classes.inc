@@ -278,7 +278,7 @@ __global__ void __launch_bounds__(256) k_upmcrit_bwd_w(const float* __restrict__
 #define MCRIT_KINDS(K_, STMT) \
     do { if (K_ == TCCT_MCRIT_CE) { constexpr int KIND = TCCT_MCRIT_CE; STMT; } else { constexpr int KIND = TCCT_MCRIT_DICE; STMT; } } while (0)     /* dice, dice2, iou: one sums kernel */
 #define MCRIT_ARGS_OK(what) \
-    TCCT_CHECK(C >= 2 && C <= MAXC, what ": C=%d unsupported (2..%d)", C, MAXC); \
+    TCCT_CHECK(C >= 2 && C <= MAXC, what ": C=%d unsupported (2..16)", C); \
     TCCT_CHECK(kind >= TCCT_MCRIT_DICE && kind <= TCCT_MCRIT_CE, what ": kind=%d unknown (0 dice, 1 dice2, 2 iou, 3 ce)", kind); \
     TCCT_CHECK(B >= 1 && B <= 65535, what ": batch %d unsupported (1..65535)", B)
 #define MCRIT_UP_OK(what) \
@@ -293,9 +293,9 @@ static int mcrit_launch_sums(const void* logits, const uint8_t* labels, int B, i
                                                               class_w, sums)));
     return 0;
 }
-static int mcrit_launch_upsums(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, double* sums,
+static int mcrit_launch_upsums(const char* what, const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, double* sums,
                                hipStream_t st) {
-    MCRIT_UP_OK("upmcrit");
+    MCRIT_UP_OK(what);
     UPDICE_SCALES(Sc, MCRIT_KINDS(kind, hipLaunchKernelGGL((k_upmcrit_sums<S, KIND>), dim3(tcct_grid((int64_t)H * w, UDB, mcrit_sums_cap(B)), B), dim3(UDB), 0, st, low, labels, h, w, H, W,
                                                            C, (float)h / (float)H, class_w, sums)));
     return 0;
@@ -303,7 +303,8 @@ static int mcrit_launch_upsums(const float* low, const uint8_t* labels, int B, i
 static int tcct_softmax_mcrit_fwd_impl(const void* logits, const uint8_t* labels, int B, int64_t HW, int C, int kind, const float* class_w, double* sums, float* loss,
                                        int dtype, tcct_stream_t stream) {
     MCRIT_ARGS_OK("softmax_mcrit_fwd");
-    TCCT_CHECK(HW >= 1, "softmax_mcrit_fwd: empty tensor");
+    TCCT_CHECK(HW >= 1, "softmax_mcrit_fwd: HW=%lld: empty tensor (HW >= 1)", (long long)HW);
+    LOSS_DTYPE_OK("softmax_mcrit_fwd");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C * B, st) != hipSuccess) { tcct_set_error("softmax_mcrit_fwd: memset failed"); return -2; }
     if (int rc = mcrit_launch_sums(logits, labels, B, HW, C, kind, class_w, sums, dtype, st)) return rc;
@@ -313,7 +314,8 @@ static int tcct_softmax_mcrit_fwd_impl(const void* logits, const uint8_t* labels
 static int tcct_softmax_mcrit_bwd_impl(const void* logits, const uint8_t* labels, int B, int64_t HW, int C, int kind, const float* class_w, const double* sums,
                                        const float* grad_out, float grad_scale, void* dlogits, int dtype, tcct_stream_t stream) {
     MCRIT_ARGS_OK("softmax_mcrit_bwd");
-    TCCT_CHECK(HW >= 1, "softmax_mcrit_bwd: empty tensor");
+    TCCT_CHECK(HW >= 1, "softmax_mcrit_bwd: HW=%lld: empty tensor (HW >= 1)", (long long)HW);
+    LOSS_DTYPE_OK("softmax_mcrit_bwd");
     const int gx = tcct_grid(HW, LB, B >= (1 << 16) ? 1 : (1 << 16) / B);
     TCCT_DISPATCH(dtype, hipLaunchKernelGGL(k_mcrit_bwd<T>, dim3(gx, B), dim3(LB), 0, (hipStream_t)stream, (const T*)logits, labels, B, HW, C, kind, class_w, sums, grad_out,
                                             grad_scale, (T*)dlogits));
@@ -322,9 +324,10 @@ static int tcct_softmax_mcrit_bwd_impl(const void* logits, const uint8_t* labels
 static int tcct_upmcrit_fwd_impl(const float* low, const uint8_t* labels, int B, int h, int w, int H, int W, int C, int kind, const float* class_w, double* sums, float* loss,
                                  tcct_stream_t stream) {
     MCRIT_ARGS_OK("upmcrit_fwd");
+    { MCRIT_UP_OK("upmcrit_fwd"); }
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(sums, 0, sizeof(double) * 3 * C * B, st) != hipSuccess) { tcct_set_error("upmcrit_fwd: memset failed"); return -2; }
-    if (int rc = mcrit_launch_upsums(low, labels, B, h, w, H, W, C, kind, class_w, sums, st)) return rc;
+    if (int rc = mcrit_launch_upsums("upmcrit_fwd", low, labels, B, h, w, H, W, C, kind, class_w, sums, st)) return rc;
     hipLaunchKernelGGL(k_mcrit_finalize, dim3(1), dim3(64), 0, st, sums, B, C, 1, 1.f, kind, (double)H * W, loss);
     TCCT_LAUNCH_OK();
 }
@@ -344,14 +347,19 @@ static int tcct_upmcrit_bwd_impl(const float* low, const uint8_t* labels, int B,
 static int tcct_mcrit_ds_fwd_impl(const void* logits, int dtype, const uint8_t* labels, int B, int H, int W, int C, const float* const* lows, const int* lh, const int* lw,
                                   int nlow, float coff, int kind, const float* class_w, double* sums, float* loss, tcct_stream_t stream) {
     MCRIT_ARGS_OK("mcrit_ds_fwd");
-    TCCT_CHECK(nlow >= 0 && nlow <= 3 && H >= 1 && W >= 1, "mcrit_ds_fwd: %d low-resolution heads (0..3), %dx%dx%d", nlow, B, H, W);
+    TCCT_CHECK(nlow >= 0 && nlow <= 3 && H >= 1 && W >= 1, "mcrit_ds_fwd: %d low-resolution heads (0..3), %dx%dx%d (H, W >= 1)", nlow, B, H, W);
+    LOSS_DTYPE_OK("mcrit_ds_fwd");
+    for (int i = 0; i < nlow; ++i) {
+        const int h = lh[i], w = lw[i];
+        MCRIT_UP_OK("mcrit_ds_fwd");
+    }
     hipStream_t st = (hipStream_t)stream;
     const size_t per_head = (size_t)B * 3 * C;
     if (hipMemsetAsync(sums, 0, sizeof(double) * per_head * (1 + nlow), st) != hipSuccess) { tcct_set_error("mcrit_ds_fwd: memset failed"); return -2; }
     const int64_t HW = (int64_t)H * W;
     if (int rc = mcrit_launch_sums(logits, labels, B, HW, C, kind, class_w, sums, dtype, st)) return rc;
     for (int i = 0; i < nlow; ++i)
-        if (int rc = mcrit_launch_upsums(lows[i], labels, B, lh[i], lw[i], H, W, C, kind, class_w, sums + (size_t)(i + 1) * per_head, st)) return rc;
+        if (int rc = mcrit_launch_upsums("mcrit_ds_fwd", lows[i], labels, B, lh[i], lw[i], H, W, C, kind, class_w, sums + (size_t)(i + 1) * per_head, st)) return rc;
     hipLaunchKernelGGL(k_mcrit_finalize, dim3(1), dim3(64), 0, st, sums, B, C, 1 + nlow, coff, kind, (double)HW, loss);
     TCCT_LAUNCH_OK();
 }
